@@ -12,7 +12,11 @@ is overwritten; the host-delivered, PCIe-bound rate is reported beside it, never
 Rank 0 prints ONE JSON line:
   roofline      dominant kernel zk_expand (HBM-write bound): achieved = (32 W + I) bytes x emails per
                 launch / average launch duration, HIP events on the launch stream inside the timed
-                region.  `traffic` = HBM bytes per launch from PMC counters collected IN THIS
+                region.
+A plain run stops there.  With --full (N=1) the line also holds the side measurements, each taking
+runs of its own after the timed steps:
+  roofline      alone_frac (zk_expand with the chip to itself), box_fill_GBps (a plain fill of the
+                same buffer), and `traffic` = HBM bytes per launch from PMC counters collected IN THIS
                 INVOCATION (two separate `rocprofv3 --pmc` child passes of a 1-step run of the same
                 workload, WRITE_SIZE and FETCH_SIZE, corrected as MI355X_MICROARCH.md prescribes),
                 or null with the reason in `traffic_source`.
@@ -20,6 +24,10 @@ Rank 0 prints ONE JSON line:
                 host cores (all-core and single-thread), buffers pre-touched (rank 0, N=1 only).
   other_configs BASELINE.json configs[1] (batch 256), configs[4] (maxBody 65536, batch 1024; fewer
                 steps) and the delivered-to-host (PCIe-inclusive) rate, measured in the same run.
+
+--dump-outputs DIR writes what the last timed step handed its caller as float64 .npy files (every
+32-bit word of the outputs exactly), so that two builds can be compared output for output; the
+inputs are a function of the command line only (seeded synthetic emails).
 """
 import argparse
 import csv
@@ -232,6 +240,64 @@ def timed(torch, fn, steps, warmup):
     return time.perf_counter() - t0
 
 
+def last_expanded(pl):
+    """(ring buffer, batch index of its first email) of the tile the pipeline expanded last: the step's last tile, or with
+    --no-overlap 2 (the expansion lags one sub-batch behind) the last tile of the sub-batch before the step's last one"""
+    sb = pl.nsub - 1 if pl.serial != 2 else (pl.nsub - 2) % pl.nsub
+    k = sb * pl.tiles_per_sub + pl.tiles_per_sub - 1
+    return pl.d_out[k % len(pl.d_out)], sb * pl.prep + (pl.tiles_per_sub - 1) * pl.tile
+
+
+def save_outputs(out_dir, arrays):
+    """arrays: name -> float64 ndarray, written as out_dir/<name>.npy (64 MB at most in all)"""
+    import numpy as np
+    total = sum(a.nbytes for a in arrays.values())
+    assert total <= 64 << 20, f"--dump-outputs: {total} bytes exceed 64 MB"
+    os.makedirs(out_dir, exist_ok=True)
+    for name, a in arrays.items():
+        assert a.dtype == np.float64
+        np.save(os.path.join(out_dir, name + ".npy"), a)
+
+
+def words_f64(a):
+    """uint8 ndarray [..., 4k] -> float64 [..., k] of its little-endian 32-bit words (exact)"""
+    import numpy as np
+    return np.ascontiguousarray(a).view("<u4").astype(np.float64)
+
+
+def dump_witness_outputs(out_dir, torch, pl, table, first_email):
+    """--dump-outputs of the witness pipeline.  The caller of the timed path holds the result table (status + the outputs
+    w[1..3] of every email of the job) and the witnesses of the tile expanded last in its HBM ring (57 MB each at the headline
+    circuit, so a fixed, seeded sample of them plus a checksum of every word):
+      status.npy                 [emails]          int32 status per email
+      result_table.npy           [emails, 25]      the table's 32-bit words (status, pubkeyHash, shaHi, shaLo)
+      witness_sample.npy         [8, 65536, 8]     32-bit words of 65,536 seeded field elements of 8 seeded witnesses
+      witness_sample_emails.npy  [8]               their email indices in the job
+      witness_sample_elements.npy [65536]          their element indices in the witness
+      witness_word_sums.npy      [tile, 2]         per witness of that tile: sums of the low and of the high 16 bits of all its words"""
+    import numpy as np
+    torch.cuda.synchronize()
+    tb = table.cpu().numpy()
+    arrays = {"status": tb[:, :4].copy().view("<i4").reshape(-1).astype(np.float64), "result_table": words_f64(tb)}
+    o, lo = last_expanded(pl)
+    rows = o.view(pl.tile, pl.stride)[:, :pl.unit_bytes]
+    n_el = pl.unit_bytes // 32
+    rng = np.random.default_rng(0x5A4B)
+    em = np.sort(rng.choice(pl.tile, size=min(8, pl.tile), replace=False))
+    el = np.sort(rng.choice(n_el, size=min(65536, n_el), replace=False))
+    sel = rows[torch.from_numpy(em).to(o.device)].view(len(em), n_el, 32)[:, torch.from_numpy(el).to(o.device)]
+    arrays["witness_sample"] = words_f64(sel.cpu().numpy())
+    arrays["witness_sample_emails"] = (first_email + lo + em).astype(np.float64)
+    arrays["witness_sample_elements"] = el.astype(np.float64)
+    sums = torch.empty((pl.tile, 2), dtype=torch.int64, device=o.device)
+    for i in range(0, pl.tile, 16):
+        w = rows[i:i + 16].contiguous().view(torch.int32)
+        sums[i:i + 16, 0] = (w & 0xFFFF).sum(dim=1, dtype=torch.int64)
+        sums[i:i + 16, 1] = ((w >> 16) & 0xFFFF).sum(dim=1, dtype=torch.int64)
+    arrays["witness_word_sums"] = sums.cpu().numpy().astype(np.float64)     # < 2^44: exact
+    save_outputs(out_dir, arrays)
+
+
 def expand_roofline(c, tile):
     summ = c.timing_summary()
     ex_ms, ex_launches, _ = summ["zk_expand"]
@@ -343,6 +409,10 @@ def prove_main(args, torch, dist, backend, dev, rank, world, local_rank):
         tt = torch.tensor([dt], dtype=torch.float64, device=dev if backend == "nccl" else "cpu")
         dist.all_reduce(tt, op=dist.ReduceOp.MAX)
         dt = float(tt.item())
+    if rank == 0 and args.dump_outputs:
+        # what rank 0 holds after the last step: status + proof (pi_a, pi_b, pi_c) per email of the job
+        t = state["table"].cpu().numpy()
+        save_outputs(args.dump_outputs, {"status": t[:, :4].copy().view("<i4").reshape(-1).astype("float64"), "proof_table": words_f64(t)})
     if rank == 0:
         tab = bytes(state["table"].cpu().numpy().tobytes())
         bad = sum(1 for i in range(pb * world) if tab[260 * i:260 * i + 4] != bytes(4))
@@ -417,6 +487,12 @@ def main():
     ap.add_argument("--launch-check", action="store_true",
                     help="only rendezvous (gloo, no GPU needed): every rank joins, rank 0 prints {\"launch_check\": world} -- the "
                          "CPU test of the self-launch below")
+    ap.add_argument("--full", action="store_true",
+                    help="after the headline, also run the side measurements (N=1): roofline.alone_frac and box_fill_GBps, the PMC "
+                         "traffic passes (--pmc-traffic), other_configs (--other-configs) and cpu_baseline (--cpu-sample); "
+                         "off: set up, warm up, time the steps, print the line")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step computed to DIR/<name>.npy (float64; see dump_witness_outputs)")
     args = ap.parse_args()
 
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
@@ -531,8 +607,10 @@ def main():
         dt = float(tt.item())
     summ, ex_avg, ex_launches, achieved = expand_roofline(c, tile)
     c.set_timing(False)
+    if args.dump_outputs and rank == 0:
+        dump_witness_outputs(args.dump_outputs, torch, pl, state["table"], 0)
     alone = None
-    if world == 1 and not args.no_overlap:
+    if world == 1 and not args.no_overlap and args.full:
         # the same kernel with the chip to itself (every prepare waits for the previous sub-batch's expansions): what the
         # prepare kernels beside the stream cost it -- reported as roofline.alone_frac, outside the timed region
         pl.serial = True
@@ -581,39 +659,42 @@ def main():
             res["roofline"]["alone_frac"] = round(alone[1] / HBM_PEAK_GBS, 4)
             res["roofline"]["alone_launch_ms"] = round(alone[0], 4)
         single = world == 1
-        # same-box ceiling: a plain fill (torch.fill_, 16-byte stores) of the very buffer zk_expand just wrote,
-        # so that box-to-box variance of the HBM write rate shows beside the fraction of the spec peak
-        try:
-            buf = pl.d_out[0].view(torch.int32)
-            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-            buf.fill_(1)
-            torch.cuda.synchronize()
-            e0.record()
-            for _ in range(10):
+        if not args.full:
+            res["roofline"]["traffic_source"] = "not collected (side measurements run with --full)"
+        else:
+            # same-box ceiling: a plain fill (torch.fill_, 16-byte stores) of the very buffer zk_expand just wrote,
+            # so that box-to-box variance of the HBM write rate shows beside the fraction of the spec peak
+            try:
+                buf = pl.d_out[0].view(torch.int32)
+                e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
                 buf.fill_(1)
-            e1.record()
-            torch.cuda.synchronize()
-            fill_gbs = buf.numel() * 4 * 10 / (e0.elapsed_time(e1) * 1e-3) / 1e9
-            res["roofline"]["box_fill_GBps"] = round(fill_gbs, 1)
-            res["roofline"]["frac_of_box_fill"] = round(achieved / fill_gbs, 4)
-        except Exception as e:
-            res["roofline"]["box_fill_GBps"] = None
-            res["roofline"]["box_fill_error"] = repr(e)[:120]
-        # free the main pipeline's HBM before the side measurements
-        del pl.d_out, pl.d_scr
-        torch.cuda.empty_cache()
-        if single and args.pmc_traffic:
-            t, src = pmc_traffic(args, tile, c.W)
-            res["roofline"]["traffic"] = None if t is None else round(t)
-            res["roofline"]["traffic_source"] = src
-            if t is not None:
-                res["roofline"]["traffic_over_algorithmic"] = round(t / (bytes_per_email * tile), 4)
-        elif not single:
-            res["roofline"]["traffic_source"] = "not collected (PMC passes run at N=1 only)"
-        if single and args.other_configs:
-            res["other_configs"] = other_configs(torch, zkwg, dev, local_rank, c, args)
-        if args.cpu_sample != 0 and single:
-            res["cpu_baseline"] = cpu_baseline(c, args, fields, distinct)
+                torch.cuda.synchronize()
+                e0.record()
+                for _ in range(10):
+                    buf.fill_(1)
+                e1.record()
+                torch.cuda.synchronize()
+                fill_gbs = buf.numel() * 4 * 10 / (e0.elapsed_time(e1) * 1e-3) / 1e9
+                res["roofline"]["box_fill_GBps"] = round(fill_gbs, 1)
+                res["roofline"]["frac_of_box_fill"] = round(achieved / fill_gbs, 4)
+            except Exception as e:
+                res["roofline"]["box_fill_GBps"] = None
+                res["roofline"]["box_fill_error"] = repr(e)[:120]
+            # free the main pipeline's HBM before the side measurements
+            del pl.d_out, pl.d_scr
+            torch.cuda.empty_cache()
+            if single and args.pmc_traffic:
+                t, src = pmc_traffic(args, tile, c.W)
+                res["roofline"]["traffic"] = None if t is None else round(t)
+                res["roofline"]["traffic_source"] = src
+                if t is not None:
+                    res["roofline"]["traffic_over_algorithmic"] = round(t / (bytes_per_email * tile), 4)
+            elif not single:
+                res["roofline"]["traffic_source"] = "not collected (PMC passes run at N=1 only)"
+            if single and args.other_configs:
+                res["other_configs"] = other_configs(torch, zkwg, dev, local_rank, c, args)
+            if args.cpu_sample != 0 and single:
+                res["cpu_baseline"] = cpu_baseline(c, args, fields, distinct)
         print(json.dumps(res), flush=True)
     if dist is not None:
         dist.destroy_process_group()

@@ -1,6 +1,6 @@
 OUT=$PWD/gpurun_out; REPO=$PWD; TAG=r01_g
-timeout 600 python bench.py 2>/dev/null | tail -1 > $OUT/${TAG}_bench.json
-( cd /tmp && export TMPDIR=/tmp && timeout 600 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/${TAG}_prof -- python $REPO/bench.py --cpu-sample 0 > $OUT/${TAG}_prof_bench.json 2> $OUT/${TAG}_prof.log )
+timeout 600 python bench.py --full 2>/dev/null | tail -1 > $OUT/${TAG}_bench.json
+( cd /tmp && export TMPDIR=/tmp && timeout 600 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/${TAG}_prof -- python $REPO/bench.py --full --cpu-sample 0 > $OUT/${TAG}_prof_bench.json 2> $OUT/${TAG}_prof.log )
 python - <<PY
 import json
 for f in ("bench","prof_bench"):

@@ -5,7 +5,7 @@
 #   tests:<expr>  pytest -m gpu -k <expr>      alltests  the whole GPU suite      smoke  __graft_entry__.smoke()
 #   files:<a,b>   pytest -m gpu on these test files
 #   beside        tools/beside.py (which prepare kernel costs zk_expand how much)
-#   bench         the default bench.py line     benchq  the headline only (no PMC / other configs / CPU baseline)
+#   bench         the bench.py --full line      benchq  the headline only (no PMC / other configs / CPU baseline)
 #   prof          rocprofv3 --kernel-trace --stats of the headline pipeline
 #   rslb          removeSoftLineBreaks = 1 variant (rslb:<label> appends to <tag>_rslb_variants.json)      abc  tools/bench_abc.py      o0  tools/bench_full.py
 #   pmc:<tool.py> per-kernel HBM traffic of a tool (two rocprofv3 --pmc passes)      pmcv:<tool.py>  VALU wavefront-instructions per launch of its kernels
@@ -25,7 +25,7 @@ for step in "$@"; do
     smoke) timeout 300 python -c "import __graft_entry__ as g; g.smoke()" 2>&1 | tail -2 | tee $OUT/${TAG}_smoke.txt ;;
     beside) timeout 600 python tools/beside.py --out $OUT/${TAG}_beside.json 2>&1 | tail -20 ;;
     beside:*) timeout 600 python tools/beside.py --modes "${step#beside:}" --out $OUT/${TAG}_beside.json 2>&1 | tail -20 ;;
-    bench) timeout 1200 python bench.py 2>$OUT/${TAG}_bench.err | tail -1 > $OUT/${TAG}_bench.json
+    bench) timeout 1200 python bench.py --full 2>$OUT/${TAG}_bench.err | tail -1 > $OUT/${TAG}_bench.json
            python - <<PY
 import json
 try:

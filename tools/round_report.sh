@@ -1,6 +1,6 @@
 #!/bin/bash
 # Evidence run for one round on a GPU box (invoked through gpurun from the repo root):
-# full GPU test suite, smoke, the default bench line (with in-invocation PMC traffic, other_configs and
+# full GPU test suite, smoke, the bench.py --full line (with in-invocation PMC traffic, other_configs and
 # cpu_baseline), a rocprofv3 kernel-stats pass of the same pipeline, a VALU-instruction PMC pass for the
 # zk_rsa issue "roofline", and the removeSoftLineBreaks variant.  Everything lands in gpurun_out/<tag>_*.
 TAG=${1:-r02_final}
@@ -9,7 +9,7 @@ mkdir -p $OUT
 REPO=$PWD
 ( timeout 1800 python -m pytest tests -m gpu -q 2>&1 | tail -5 ) > $OUT/${TAG}_pytest_gpu.txt
 ( timeout 300 python -c "import __graft_entry__ as g; g.smoke(); print('smoke ok')" 2>&1 | tail -2 ) > $OUT/${TAG}_smoke.txt
-timeout 900 python bench.py 2>$OUT/${TAG}_bench.err | tail -1 > $OUT/${TAG}_bench.json
+timeout 900 python bench.py --full 2>$OUT/${TAG}_bench.err | tail -1 > $OUT/${TAG}_bench.json
 ( cd /tmp && export TMPDIR=/tmp && timeout 600 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/${TAG}_prof -- \
     python $REPO/bench.py --steps 5 --warmup 2 --cpu-sample 0 --pmc-traffic 0 --other-configs 0 > $OUT/${TAG}_prof_bench.json 2> $OUT/${TAG}_prof.log )
 ( cd /tmp && export TMPDIR=/tmp && timeout 600 rocprofv3 --kernel-trace --pmc SQ_INSTS_VALU SQ_WAVES --output-format csv -d $OUT/${TAG}_pmc_valu -- \
