@@ -17,7 +17,7 @@ third-party packages snarkjs (pinned: sampritipanda/snarkjs#fef81fc5 = 0.5.0 for
 
 "parity unpinned" for this stage: no vector of the real snarkjs exists offline; the definitions above are pinned only by
 self-consistency (ifft . fft = id, the polynomial identity below).  Pure Python integers; O(n^2) reference for small domains,
-Horner spot checks for the full size.
+an O(n log n) one (fft_fast, pinned against it) for full arrays up to 2^16, barycentric spot checks for the full size.
 """
 P = 21888242871839275222246405745257275088548364400416034343698204186575808495617
 S = 28                                   # r - 1 = 2^28 * t
@@ -67,6 +67,58 @@ def h_evaluations(a, b, c, power):
     for v in (a, b, c):
         co = ifft(list(v) + [0] * (n - len(v)))
         odd.append(fft([x * pow(inc, i, P) % P for i, x in enumerate(co)]))
+    return [(odd[0][k] * odd[1][k] - odd[2][k]) % P for k in range(n)]
+
+
+def _fft_iter(xs, w):
+    """iterative radix-2 transform X[k] = sum_j x[j] w^(j k) for a primitive len(xs)-th root w: bit-reversal permutation, then
+    log2(n) stages of Cooley-Tukey butterflies, exact in Python integers (O(n log n): the full-array reference at the sizes the
+    kernels are checked at)"""
+    n = len(xs)
+    power = n.bit_length() - 1
+    assert 1 << power == n
+    a = [0] * n
+    for i, v in enumerate(xs):
+        a[int(format(i, "0%db" % power)[::-1], 2) if power else 0] = v % P
+    half = 1
+    while half < n:
+        wm = pow(w, n // (2 * half), P)
+        tws = [1] * half
+        for j in range(1, half):
+            tws[j] = tws[j - 1] * wm % P
+        for start in range(0, n, 2 * half):
+            for j in range(half):
+                u, t = a[start + j], a[start + j + half] * tws[j] % P
+                a[start + j] = (u + t) % P
+                a[start + j + half] = (u - t) % P
+        half *= 2
+    return a
+
+
+def fft_fast(xs):
+    """Fr.fft in O(n log n): equal to fft(xs)"""
+    return _fft_iter(xs, root(len(xs).bit_length() - 1))
+
+
+def ifft_fast(xs):
+    """Fr.ifft in O(n log n): equal to ifft(xs)"""
+    n = len(xs)
+    ninv = pow(n, P - 2, P)
+    return [v * ninv % P for v in _fft_iter(xs, pow(root(n.bit_length() - 1), P - 2, P))]
+
+
+def h_evaluations_fast(a, b, c, power):
+    """h_evaluations in O(n log n)"""
+    n = 1 << power
+    inc = coset_inc(power)
+    odd = []
+    for v in (a, b, c):
+        co = ifft_fast(list(v) + [0] * (n - len(v)))
+        s, acc = [], 1
+        for x in co:
+            s.append(x * acc % P)
+            acc = acc * inc % P
+        odd.append(fft_fast(s))
     return [(odd[0][k] * odd[1][k] - odd[2][k]) % P for k in range(n)]
 
 

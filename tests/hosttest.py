@@ -86,6 +86,17 @@ def load():
     lib.ht_net_eval.argtypes = [C.c_void_p] * 5
     lib.ht_regex_scan.restype = C.c_uint32
     lib.ht_regex_scan.argtypes = [C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p]
+    # the transforms' host mirror (zkwg_ntt_core.h) and the range checks of their limb form (zkwg_fr29.h)
+    lib.ht_fr29_violations.restype = C.c_ulonglong
+    lib.ht_ntt_transform.restype = C.c_int
+    lib.ht_ntt_transform.argtypes = [C.c_uint32, C.c_uint64, C.c_int, C.c_void_p]
+    lib.ht_h_evaluations.restype = C.c_int
+    lib.ht_h_evaluations.argtypes = [C.c_uint32, C.c_void_p, C.c_uint64, C.c_uint64, C.c_uint64, C.c_void_p, C.c_uint64, C.c_void_p]
+    lib.ht_ntt_pass.restype = C.c_int
+    lib.ht_ntt_pass.argtypes = [C.c_int, C.c_int, C.c_uint32, C.c_uint32, C.c_uint32, C.c_int, C.c_int, C.c_uint32, C.c_void_p, C.c_void_p]
+    lib.ht_ntt_sched.argtypes = [C.c_uint32, C.c_void_p]
+    lib.ht_ntt_join.argtypes = [C.c_void_p] * 4
+    lib.ht_fr29_op.argtypes = [C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]
     return lib
 
 

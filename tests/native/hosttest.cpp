@@ -468,3 +468,157 @@ void ht_fq29_op(int op, const uint8_t* a, const uint8_t* b, const uint8_t* c, co
   memcpy(out, &st, 32);
 }
 }
+
+// The transforms (zkwg_ntt_core.h: the per-phase bodies of the kernels of zkwg_kernels_ntt.hip), executed here phase by phase, thread
+// by thread, in the launch order of zk_ntt_launch, with every precondition of the lazy limb form (zkwg_fr29.h) counted.  Workgroups of
+// one launch touch disjoint elements (that is what lets the device run its passes in place), so they run on several host threads.
+#define ZKWG_FR29_CHECK 1
+#include "zkwg_ntt_core.h"
+#include <thread>
+#include <atomic>
+template <class F>
+static void ht_ntt_grid(u32 gx, u32 gy, size_t lds_bytes, F body) {
+  u32 nt = std::thread::hardware_concurrency();
+  if (const char* e = getenv("OMP_NUM_THREADS")) nt = (u32)atoi(e);
+  nt = nt < 1 ? 1 : nt > 16 ? 16 : nt;
+  const u64 total = (u64)gx * gy;
+  if ((u64)nt > total) nt = (u32)total;
+  std::atomic<u64> next{0};
+  auto run = [&]() {
+    std::vector<ZkU4> lds(lds_bytes / 16 + 1);
+    for (u64 b; (b = next.fetch_add(1)) < total;) {
+      for (auto& v : lds) v = ZkU4{0xdeadbeefu, 0xdeadbeefu, 0xdeadbeefu, 0xdeadbeefu};     // what a pass reads before it writes shows
+      body((u32)(b % gx), (u32)(b / gx), lds.data());
+    }
+  };
+  std::vector<std::thread> th;
+  for (u32 i = 1; i < nt; ++i) th.emplace_back(run);
+  run();
+  for (auto& t : th) t.join();
+}
+template <bool DIT>
+static void ht_ntt_stages(const ZkLds29& y, const ZkLds29& twl, u32 G, u32 g, u32 nel, u32 C) {
+  u32 st = 0;
+  for (; st + 1u < g; st += 2u) for (u32 t = 0; t < 256u; ++t) zk_ntt_stage_pair<DIT>(y, twl, G, st, nel, C, t, 256u);
+  if (st < g) for (u32 t = 0; t < 256u; ++t) zk_ntt_stage_single<DIT>(y, twl, G, st, nel, C, t, 256u);
+}
+template <bool DIT>
+static void ht_ntt_col(const ZkNttBuf& src, const ZkNttBuf& dst, const Fr* tw, u32 L, u32 lb, u32 g, u32 inv, u32 n_polys) {
+  const ZkNttSched sc = zk_ntt_sched(L);
+  ht_ntt_grid((u32)((1ull << L) / sc.tile), n_polys, zk_ntt_lds_bytes(sc.tile, g), [&](u32 bx, u32 by, ZkU4* lds) {
+    const ZkNttColWg w = zk_ntt_col_wg(lds, L, lb, g, inv, bx, by);
+    for (u32 t = 0; t < 256u; ++t) zk_ntt_col_load<DIT>(w, src, tw, t, 256u);
+    ht_ntt_stages<DIT>(w.y, w.twl, w.G, g, w.G, w.C);
+    for (u32 t = 0; t < 256u; ++t) zk_ntt_col_store<DIT>(w, dst, tw, t, 256u);
+  });
+}
+template <bool DIT>
+static void ht_ntt_row(const ZkNttBuf& src, const ZkNttBuf& dst, const Fr* tw, const Fr* scale, const Fr& uni, u32 use_uni, u32 L, u32 g, u32 inv, u32 n_polys) {
+  const ZkNttSched sc = zk_ntt_sched(L);
+  ht_ntt_grid((u32)((1ull << L) / sc.tile), n_polys, zk_ntt_lds_bytes(sc.tile, g), [&](u32 bx, u32 by, ZkU4* lds) {
+    const ZkNttRowWg w = zk_ntt_row_wg(lds, L, g, inv, bx, by);
+    for (u32 t = 0; t < 256u; ++t) zk_ntt_row_load(w, src, tw, t, 256u);
+    ht_ntt_stages<DIT>(w.y, w.twl, w.G, g, w.TILE, 1u);
+    for (u32 t = 0; t < 256u; ++t) zk_ntt_row_store(w, dst, scale, uni, use_uni, t, 256u);
+  });
+}
+// zk_ntt_launch of zkwg_kernels_ntt.hip
+static void ht_ntt_launch(int dit, const Fr* src, u64 src_es, u64 src_ps, u64 valid, int src_lazy, void* work, Fr* out, const Fr* tw, const Fr* scale,
+                          const Fr* uni_host, u32 L, u32 n_polys, u32 inv) {
+  const Fr uni = uni_host ? *uni_host : fr_zero();
+  const u32 use_uni = uni_host ? 1u : 0u;
+  const u64 n = 1ull << L;
+  const ZkNttSched sc = zk_ntt_sched(L);
+  const ZkNttBuf W{work, 0, 0, n, 1u};
+  ZkNttBuf S = src_lazy ? W : ZkNttBuf{src, src_es, src_ps, valid, 0u};
+  const ZkNttBuf OUT{out, 3u * n, n, n, 0u};
+  if (!dit) {
+    for (u32 i = 0; i < sc.ng; ++i) { ht_ntt_col<false>(S, W, tw, L, sc.lb[i], sc.gs[i], inv, n_polys); S = W; }
+    ht_ntt_row<false>(S, out ? OUT : W, tw, scale, uni, use_uni, L, sc.g_row, inv, n_polys);
+  } else {
+    ht_ntt_row<true>(S, (sc.ng == 0 && out) ? OUT : W, tw, nullptr, uni, 0u, L, sc.g_row, inv, n_polys);
+    for (u32 i = sc.ng; i-- > 0;) ht_ntt_col<true>(W, (i == 0 && out) ? OUT : W, tw, L, sc.lb[i], sc.gs[i], inv, n_polys);
+  }
+}
+static void ht_ntt_bitrev(Fr* data, u32 L, u64 n_polys) {
+  for (u64 q = 0; q < n_polys; ++q) for (u64 i = 0; i < (1ull << L); ++i) zk_ntt_bitrev_thread(data, L, q, i);
+}
+extern "C" {
+unsigned long long ht_fr29_violations() { return zk_fr29_violations; }
+void ht_fr29_reset() { zk_fr29_violations = 0; }
+// zkwg_ntt_transform_device: n_polys x 2^L Montgomery-form words in place, natural order in and out
+int ht_ntt_transform(uint32_t L, uint64_t n_polys, int inverse, void* data) {
+  std::vector<Fr> tw, sc;
+  Fr ninv;
+  if (L < 2 || L > 26 || !zk_ntt_tables(L, tw, sc, ninv)) return -1;
+  std::vector<u8> work(36ull * (1ull << L) * n_polys);
+  Fr* d = (Fr*)data;
+  if (inverse) {
+    ht_ntt_launch(0, d, 3ull << L, 1ull << L, 1ull << L, 0, work.data(), d, tw.data(), nullptr, &ninv, L, (u32)n_polys, 1u);
+    ht_ntt_bitrev(d, L, n_polys);
+  } else {
+    ht_ntt_bitrev(d, L, n_polys);
+    ht_ntt_launch(1, d, 3ull << L, 1ull << L, 1ull << L, 0, work.data(), d, tw.data(), nullptr, nullptr, L, (u32)n_polys, 0u);
+  }
+  return 0;
+}
+// zkwg_h_evaluations_device: E records of A.w | B.w | C.w (m rows each, Montgomery form) `abc_stride` bytes apart -> out (2^L words per
+// email, `out_stride` bytes apart); `work` (3 E 36 2^L bytes) keeps the limb-form buffer for the caller when given
+int ht_h_evaluations(uint32_t L, const void* abc, uint64_t abc_stride, uint64_t m, uint64_t E, void* out, uint64_t out_stride, void* work_out) {
+  std::vector<Fr> tw, sc;
+  Fr ninv;
+  const u64 n = 1ull << L;
+  if (L < 2 || L > 26 || m > n || (abc_stride & 31) || (out_stride & 31) || !zk_ntt_tables(L, tw, sc, ninv)) return -1;
+  std::vector<u8> wv(work_out ? 0 : 3ull * n * 36 * E);
+  void* work = work_out ? work_out : wv.data();
+  const u32 np = (u32)(3 * E);
+  ht_ntt_launch(0, (const Fr*)abc, abc_stride / 32, m, m, 0, work, nullptr, tw.data(), sc.data(), nullptr, L, np, 1u);
+  ht_ntt_launch(1, nullptr, 0, 0, n, 1, work, nullptr, tw.data(), nullptr, nullptr, L, np, 0u);
+  const ZkNttBuf W{work, 0, 0, n, 1u};
+  for (u64 e = 0; e < E; ++e) for (u64 i = 0; i < n; ++i) zk_ntt_join_thread(W, (Fr*)out, n, out_stride / 32, e, i);
+  return 0;
+}
+// one pass of zk_ntt_launch on a planar limb-form buffer (n_polys x 36 2^L bytes) in place: kind 0 = column pass i of the schedule,
+// 1 = the row pass; `canon` (n_polys x 2^L words) receives canonical words instead when given.  With scale = 1 the DIF row pass
+// multiplies by the plan's scale table (the pipeline's inverse transforms), with uni = 1 by 1 / n.
+int ht_ntt_pass(int kind, int dit, uint32_t L, uint32_t i, uint32_t inv, int scale, int uni, uint32_t n_polys, void* work, void* canon) {
+  std::vector<Fr> tw, sc;
+  Fr ninv;
+  const u64 n = 1ull << L;
+  const ZkNttSched s = zk_ntt_sched(L);
+  if (L < 2 || L > 26 || (kind == 0 && i >= s.ng) || !zk_ntt_tables(L, tw, sc, ninv)) return -1;
+  const ZkNttBuf W{work, 0, 0, n, 1u};
+  const ZkNttBuf D = canon ? ZkNttBuf{canon, 3u * n, n, n, 0u} : W;
+  if (kind == 0) {
+    if (dit) ht_ntt_col<true>(W, D, tw.data(), L, s.lb[i], s.gs[i], inv, n_polys);
+    else ht_ntt_col<false>(W, D, tw.data(), L, s.lb[i], s.gs[i], inv, n_polys);
+  } else {
+    if (dit) ht_ntt_row<true>(W, D, tw.data(), nullptr, fr_zero(), 0u, L, s.g_row, inv, n_polys);
+    else ht_ntt_row<false>(W, D, tw.data(), scale ? sc.data() : nullptr, ninv, uni ? 1u : 0u, L, s.g_row, inv, n_polys);
+  }
+  return 0;
+}
+// the schedule: np, ng, g_row, tile, gs[0 .. np), lb[0 .. np)
+void ht_ntt_sched(uint32_t L, uint32_t* out) {
+  const ZkNttSched s = zk_ntt_sched(L);
+  out[0] = s.np; out[1] = s.ng; out[2] = s.g_row; out[3] = s.tile;
+  for (u32 i = 0; i < s.np; ++i) { out[4 + i] = s.gs[i]; out[12 + i] = s.lb[i]; }
+}
+// one element of zk_ntt_join: limb-form a, b, c (9 words each) -> canonical words
+void ht_ntt_join(const uint32_t* a, const uint32_t* b, const uint32_t* c, void* out) {
+  Fr29 x, y, z;
+  memcpy(x.l, a, 36); memcpy(y.l, b, 36); memcpy(z.l, c, 36);
+  *(Fr*)out = zk_ntt_join_value(x, y, z);
+}
+// the checker itself: op 0 = fr29_to_fr_v<32>(a), 1 = fr29_sub<4, 1>(a, b), 2 = fr29_mul(a, b), 3 = fr29_norm(a); result limbs in out
+void ht_fr29_op(int op, const uint32_t* a, const uint32_t* b, uint32_t* out) {
+  Fr29 x, y;
+  memcpy(x.l, a, 36); memcpy(y.l, b, 36);
+  Fr29 r = fr29_zero();
+  if (op == 0) { const Fr f = fr29_to_fr_v<32>(x); r = fr29_from_fr(f); }
+  else if (op == 1) r = fr29_sub<4, 1>(x, y);
+  else if (op == 2) r = fr29_mul(x, y);
+  else r = fr29_norm(x);
+  memcpy(out, r.l, 36);
+}
+}

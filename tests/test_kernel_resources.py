@@ -14,12 +14,12 @@ from conftest import ROOT
 CSRC = os.path.join(ROOT, "zk-email-verify_amd", "csrc")
 
 
-_SOURCES = ("zkwg_kernels_rslb.hip", "zkwg_kernels_expand3.hip", "zkwg_kernels_msm.hip")
+_SOURCES = ("zkwg_kernels_rslb.hip", "zkwg_kernels_expand3.hip", "zkwg_kernels_msm.hip", "zkwg_kernels_ntt.hip")
 _compiles = {}
 
 
 def _start_compiles(tmpdir):
-    """the three cross-compilations of this module run side by side (each is one hipcc process of 30-60 s)"""
+    """the four cross-compilations of this module run side by side (each is one hipcc process of 30-60 s)"""
     hipcc = shutil.which("hipcc") or "/opt/rocm/bin/hipcc"
     for src in _SOURCES:
         if src not in _compiles:
@@ -103,3 +103,20 @@ def test_multi_exponentiation_kernels_use_no_scratch_memory(tmp_path):
     assert all(v["Occupancy"] >= 4 for v in hot1), hot1
     assert all(v["Occupancy"] >= 3 for v in hot2), hot2
     assert all(v["Occupancy"] >= 2 for n, v in ks.items()), ks
+
+
+@pytest.mark.skipif(not (shutil.which("hipcc") or os.path.exists("/opt/rocm/bin/hipcc")), reason="hipcc not available")
+def test_transform_kernels_use_no_scratch_memory_and_keep_their_registers(tmp_path):
+    """every zk_ntt_* kernel of the prover's transforms: no scratch, and no more VGPRs / no less occupancy than the kernels had before
+    their bodies moved into zkwg_ntt_core.h (shared with the host mirror of the CPU tests).  The products keep a 9-limb value and its
+    18 partial products in registers; a spill would put them in scratch."""
+    info = _resource_usage("zkwg_kernels_ntt.hip", tmp_path / "ntt.o")
+    ks = {n: v for n, v in info.items() if "zk_ntt_" in n}
+    assert len(ks) == 6, sorted(info)
+    for n, v in ks.items():
+        assert v.get("ScratchSize") == 0, (n, v)
+    # (name fragment, VGPRs, occupancy) as compiled before the refactor
+    for frag, vgprs, occ in (("zk_ntt_colILb0E", 120, 4), ("zk_ntt_colILb1E", 126, 4), ("zk_ntt_rowILb0E", 120, 4), ("zk_ntt_rowILb1E", 119, 4),
+                             ("zk_ntt_join", 53, 8), ("zk_ntt_bitrev", 23, 8)):
+        v = next(v for n, v in ks.items() if frag in n)
+        assert v["VGPRs"] + v.get("AGPRs", 0) <= vgprs and v["Occupancy"] >= occ, (frag, v)

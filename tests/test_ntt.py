@@ -49,6 +49,17 @@ def _from_dev(t, mont=True):
     return [int.from_bytes(raw[i:i + 32], "little") * (rinv if mont else 1) % ntt.P for i in range(0, len(raw), 32)]
 
 
+def _canon_from_dev(t):
+    """the values of an OUTPUT array: every raw word must be canonical (< r) before it is read as x 2^256 mod r"""
+    from oracle.pyref import ntt
+    raw = t.cpu().numpy().tobytes()
+    words = [int.from_bytes(raw[i:i + 32], "little") for i in range(0, len(raw), 32)]
+    bad = [i for i, w in enumerate(words) if w >= ntt.P]
+    assert not bad, ("non-canonical output words", bad[:8])
+    rinv = pow(R, ntt.P - 2, ntt.P)
+    return [w * rinv % ntt.P for w in words]
+
+
 @pytest.mark.gpu
 @pytest.mark.parametrize("power", [2, 3, 6, 8, 9, 10, 11, 13, 19])
 def test_transforms_match_the_oracle(power):
@@ -64,7 +75,7 @@ def test_transforms_match_the_oracle(power):
     d = _to_dev(torch, [v for x in xs for v in x])
     plan.transform_device(d, polys)
     torch.cuda.synchronize()
-    got = _from_dev(d)
+    got = _canon_from_dev(d)
     w = ntt.root(power)
     for q, x in enumerate(xs):
         if power <= 6:
@@ -78,7 +89,7 @@ def test_transforms_match_the_oracle(power):
                 assert got[q * n + k] == acc, (q, k)
     plan.transform_device(d, polys, inverse=True)
     torch.cuda.synchronize()
-    assert _from_dev(d) == [v for x in xs for v in x]
+    assert _canon_from_dev(d) == [v for x in xs for v in x]
 
 
 @pytest.mark.gpu
@@ -105,7 +116,7 @@ def test_h_evaluations_match_the_oracle(power, m):
     d_out = torch.zeros(emails * 32 * n, dtype=torch.uint8, device="cuda:0")
     plan.h_evaluations_device(d_abc, stride, m, emails, d_work, d_out)
     torch.cuda.synchronize()
-    got = _from_dev(d_out)
+    got = _canon_from_dev(d_out)
     for e in range(emails):
         a, b, c = abc[e]
         if power <= 8:
@@ -175,6 +186,7 @@ def test_h_evaluations_on_the_headline_domain():
     torch.cuda.synchronize()
     got = d_out.cpu().numpy().tobytes()
     rinv = pow(R, ntt.P - 2, ntt.P)
+    assert _all_canonical(got)
     for e in range(emails):
         polys = []
         for j in range(3):
@@ -221,7 +233,109 @@ def test_h_evaluations_of_the_real_test_eml_from_the_image():
     vals = _from_dev(d_abc)
     a, b, cc = vals[:m], vals[m:2 * m], vals[2 * m:]
     assert all((a[i] * b[i] - cc[i]) % ntt.P == 0 for i in range(0, m, 997))       # the witness satisfies its constraints
-    got = _from_dev(d_out)
+    got = _canon_from_dev(d_out)
     for k in (1, (1 << 20) - 3):
         want = (ntt.coset_eval_direct(a, 20, k) * ntt.coset_eval_direct(b, 20, k) - ntt.coset_eval_direct(cc, 20, k)) % ntt.P
         assert got[k] == want and want != 0
+
+
+# ---- device = host mirror, byte for byte over whole arrays (tests/native/hosttest.cpp runs the kernels' phases of csrc/zkwg_ntt_core.h) --
+def _all_canonical(raw):
+    """every 32-byte little-endian word of `raw` below r (numpy, whole arrays)"""
+    import numpy as np
+    from oracle.pyref import ntt
+    w = np.frombuffer(raw, dtype="<u8").reshape(-1, 4)
+    p = [(ntt.P >> (64 * k)) & (2 ** 64 - 1) for k in (3, 2, 1, 0)]
+    below = np.zeros(len(w), dtype=bool)
+    equal = np.ones(len(w), dtype=bool)
+    for k, pk in zip((3, 2, 1, 0), p):
+        below |= equal & (w[:, k] < np.uint64(pk))
+        equal &= w[:, k] == np.uint64(pk)
+    return bool(below.all())
+
+
+def _words_np(rng, fam, count):
+    """canonical Montgomery-form words of one input family, as a (count, 4) uint64 array"""
+    import numpy as np
+    from oracle.pyref import ntt
+    split = lambda x: [(x >> (64 * k)) & (2 ** 64 - 1) for k in range(4)]
+    if fam == "uniform":
+        w = rng.integers(0, 2 ** 64, size=(count, 4), dtype=np.uint64)
+        w[:, 3] &= np.uint64(0x2fffffffffffffff)             # below r's top word: canonical
+        return w
+    if fam == "top":
+        return np.tile(np.array(split(ntt.P - 1), dtype=np.uint64), (count, 1))
+    if fam == "alternating":
+        w = np.zeros((count, 4), dtype=np.uint64)
+        w[1::2] = split(ntt.P - 1)
+        return w
+    lut = np.array([split(v * R % ntt.P) for v in (0, 1, 2, 255)], dtype=np.uint64)     # witness-like: bits and bytes
+    return lut[rng.choice(4, size=count, p=[0.45, 0.4, 0.1, 0.05])]
+
+
+def _mirror():
+    import hosttest
+    return hosttest.load()
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("power", [2, 7, 8, 10, 13, 14, 16])
+def test_transforms_equal_the_host_mirror_over_whole_arrays(power):
+    """both directions, four polynomials of the four input families: the device's output bytes are the mirror's, every word canonical"""
+    import ctypes as C
+    import numpy as np
+    import torch
+    import zkwg
+    lib = _mirror()
+    rng = np.random.default_rng(power)
+    n = 1 << power
+    x = np.concatenate([_words_np(rng, f, n) for f in ("uniform", "top", "alternating", "witness")])
+    plan = zkwg.Ntt(power)
+    for inverse in (False, True):
+        d = torch.from_numpy(x.view(np.uint8).reshape(-1).copy()).to("cuda:0")
+        plan.transform_device(d, 4, inverse=inverse)
+        torch.cuda.synchronize()
+        got = d.cpu().numpy().tobytes()
+        host = bytearray(x.tobytes())
+        lib.ht_fr29_reset()
+        assert lib.ht_ntt_transform(power, 4, 1 if inverse else 0, (C.c_char * len(host)).from_buffer(host)) == 0
+        assert lib.ht_fr29_violations() == 0
+        assert _all_canonical(got)
+        assert got == bytes(host), inverse
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("power,m,emails", [(2, 3, 2), (7, 100, 3), (8, 256, 2), (10, 1000, 3), (13, 8000, 2), (14, 16383, 2), (16, 60001, 2),
+                                            (20, 1000003, 1)])
+def test_h_evaluations_equal_the_host_mirror_over_whole_arrays(power, m, emails):
+    """m rows (not a multiple of the tile) zero-padded to the domain, several emails with padded record and output strides: the device's
+    output bytes are the mirror's over every email, every word canonical; the headline pass split 7 / 7 / 6 at 2^20"""
+    import ctypes as C
+    import numpy as np
+    import torch
+    import zkwg
+    lib = _mirror()
+    rng = np.random.default_rng(1000 + power)
+    n = 1 << power
+    fams = ("uniform", "witness", "top", "alternating")
+    stride_w, out_w = 3 * m + 2, n + 3                        # (words) padded record / output strides
+    abc = np.zeros((emails, stride_w, 4), dtype=np.uint64)
+    for e in range(emails):
+        abc[e, :3 * m] = _words_np(rng, fams[e % len(fams)] if power < 20 else "witness", 3 * m)
+    d_abc = torch.from_numpy(abc.view(np.uint8).reshape(-1).copy()).to("cuda:0")
+    plan = zkwg.Ntt(power)
+    d_work = torch.empty(plan.work_bytes(emails), dtype=torch.uint8, device="cuda:0")
+    d_out = torch.zeros(emails * 32 * out_w, dtype=torch.uint8, device="cuda:0")
+    plan.h_evaluations_device(d_abc, 32 * stride_w, m, emails, d_work, d_out, out_stride=32 * out_w)
+    torch.cuda.synchronize()
+    got = d_out.cpu().numpy().tobytes()
+    host_in = bytearray(abc.tobytes())
+    host_out = bytearray(emails * 32 * out_w)
+    lib.ht_fr29_reset()
+    assert lib.ht_h_evaluations(power, (C.c_char * len(host_in)).from_buffer(host_in), 32 * stride_w, m, emails,
+                                (C.c_char * len(host_out)).from_buffer(host_out), 32 * out_w, None) == 0
+    assert lib.ht_fr29_violations() == 0
+    for e in range(emails):
+        dev = got[32 * out_w * e:32 * (out_w * e + n)]
+        assert _all_canonical(dev), e
+        assert dev == bytes(host_out[32 * out_w * e:32 * (out_w * e + n)]), e

@@ -10,6 +10,10 @@
 // Values are kept in limb form between products.  A product accepts one operand `a` with limbs < 3 * 2^30 (sums and differences of
 // products need no carry propagation first) and one operand `b` with limbs < 2^29 (a twiddle / table constant), and returns limbs
 // < 2^29 (the top one < 2^32) with value < a b / 2^261 + r.
+//
+// The host build can count every violated precondition (ZKWG_FR29_CHECK: tests/native/hosttest.cpp, asserted zero by
+// tests/test_ntt_cpu.py): column sums of a product, limb dominance of a subtraction's constant, u32 wrap of a sum, and the value bounds
+// of the conversions back to words, all in exact integer arithmetic.
 #pragma once
 #include "zkwg_fr.h"
 
@@ -18,6 +22,66 @@ struct Fr29 {
 };
 #define ZK29_M 0x1fffffffu
 #define ZK29_N0 0x0fffffffu      // -r^-1 mod 2^29
+
+#if !defined(__HIP_DEVICE_COMPILE__) && defined(ZKWG_FR29_CHECK)
+#include <atomic>
+static std::atomic<unsigned long long> zk_fr29_violations{0};     // (the host mirror runs workgroups on several threads)
+#define ZKR29_EXPECT(cond) do { if (!(cond)) ++zk_fr29_violations; } while (0)
+// exact values of limb forms: 18 words of 32 bits (a product of two limb-form values is below 2^528)
+struct ZkR29Big { u32 w[18]; };
+static inline ZkR29Big zkr29_big(const u32 l[9]) {
+  ZkR29Big r{};
+  for (int i = 0; i < 9; ++i) {
+    const int bit = 29 * i;
+    unsigned __int128 c = (unsigned __int128)l[i] << (bit & 31);
+    for (int k = bit >> 5; c && k < 18; ++k) { c += r.w[k]; r.w[k] = (u32)c; c >>= 32; }
+  }
+  return r;
+}
+static inline ZkR29Big zkr29_big_mul(const ZkR29Big& a, const ZkR29Big& b) {
+  ZkR29Big r{};
+  for (int i = 0; i < 18; ++i) {
+    u64 c = 0;
+    for (int j = 0; i + j < 18; ++j) { c += (u64)a.w[i] * b.w[j] + r.w[i + j]; r.w[i + j] = (u32)c; c >>= 32; }
+  }
+  return r;
+}
+static inline ZkR29Big zkr29_big_add(const ZkR29Big& a, const ZkR29Big& b) {
+  ZkR29Big r{};
+  u64 c = 0;
+  for (int k = 0; k < 18; ++k) { c += (u64)a.w[k] + b.w[k]; r.w[k] = (u32)c; c >>= 32; }
+  return r;
+}
+static inline ZkR29Big zkr29_big_shl(const ZkR29Big& a, int s) {
+  ZkR29Big r{};
+  for (int k = 17; k >= 0; --k) {
+    const int src = k - (s >> 5);
+    u64 v = src >= 0 ? (u64)a.w[src] << (s & 31) : 0;
+    if (src - 1 >= 0 && (s & 31)) v |= (u64)a.w[src - 1] >> (32 - (s & 31));
+    r.w[k] = (u32)v;
+  }
+  return r;
+}
+static inline int zkr29_big_cmp(const ZkR29Big& a, const ZkR29Big& b) {
+  for (int k = 17; k >= 0; --k) if (a.w[k] != b.w[k]) return a.w[k] < b.w[k] ? -1 : 1;
+  return 0;
+}
+static inline ZkR29Big zkr29_big_kr(u64 k) {    // k r
+  const u64 p[4] = {ZK_P0, ZK_P1, ZK_P2, ZK_P3};
+  ZkR29Big r{};
+  unsigned __int128 c = 0;
+  for (int i = 0; i < 4; ++i) {
+    c += (unsigned __int128)k * p[i];
+    r.w[2 * i] = (u32)c; r.w[2 * i + 1] = (u32)(c >> 32); c >>= 64;
+  }
+  r.w[8] = (u32)c; r.w[9] = (u32)(c >> 32);
+  return r;
+}
+// value of `l` below k r
+static inline bool zkr29_below_kr(const u32 l[9], u64 k) { return zkr29_big_cmp(zkr29_big(l), zkr29_big_kr(k)) < 0; }
+#else
+#define ZKR29_EXPECT(cond) do { } while (0)
+#endif
 
 ZK_HD Fr29 fr29_from_fr(const Fr& x) {
   Fr29 r;
@@ -37,6 +101,7 @@ ZK_HD Fr fr29_to_fr(const Fr29& x) {
   u64 c = 0;
 #pragma unroll
   for (int i = 0; i < 9; ++i) { c += x.l[i]; t[i] = i < 8 ? (c & ZK29_M) : c; c >>= 29; }
+  ZKR29_EXPECT(t[8] < (1u << 24));                // value < 2^256
   u64 w[5] = {0, 0, 0, 0, 0};
 #pragma unroll
   for (int i = 0; i < 9; ++i) {
@@ -75,14 +140,27 @@ ZK_HD Fr29 fr29_mul(const Fr29& a, const Fr29& b) {
     r.l[k - 9] = (u32)acc & ZK29_M;
     acc >>= 29;
   }
+  ZKR29_EXPECT(acc < (1ull << 32));               // the top limb holds what is left
   r.l[8] = (u32)acc;
+#if !defined(__HIP_DEVICE_COMPILE__) && defined(ZKWG_FR29_CHECK)
+  {   // every column sum (products, reduction products, carry in) below 2^64, recomputed in 128 bits with the same q
+    unsigned __int128 c = 0;
+    for (int k = 0; k < 17; ++k) {
+      for (int i = 0; i < 9; ++i) if (k - i >= 0 && k - i < 9) c += (unsigned __int128)a.l[i] * b.l[k - i] + (unsigned __int128)q[i] * P[k - i];
+      ZKR29_EXPECT(c < ((unsigned __int128)1 << 64));
+      c >>= 29;
+    }
+    // and the value: r 2^261 < a b + r 2^261
+    ZKR29_EXPECT(zkr29_big_cmp(zkr29_big_shl(zkr29_big(r.l), 261), zkr29_big_add(zkr29_big_mul(zkr29_big(a.l), zkr29_big(b.l)), zkr29_big_shl(zkr29_big_kr(1), 261))) < 0);
+  }
+#endif
   return r;
 }
 // lazy sums: limbs add without carries; a difference adds a multiple of r whose limbs dominate a normalised subtrahend's
 ZK_HD Fr29 fr29_add(const Fr29& a, const Fr29& b) {
   Fr29 r;
 #pragma unroll
-  for (int i = 0; i < 9; ++i) r.l[i] = a.l[i] + b.l[i];
+  for (int i = 0; i < 9; ++i) { r.l[i] = a.l[i] + b.l[i]; ZKR29_EXPECT(r.l[i] >= a.l[i]); }
   return r;
 }
 
@@ -96,8 +174,9 @@ ZK_HD Fr29 fr29_norm(const Fr29& a) {
   Fr29 r;
   u32 c = 0;
 #pragma unroll
-  for (int i = 0; i < 8; ++i) { const u32 t = a.l[i] + c; r.l[i] = t & ZK29_M; c = t >> 29; }
+  for (int i = 0; i < 8; ++i) { const u32 t = a.l[i] + c; ZKR29_EXPECT(t >= c); r.l[i] = t & ZK29_M; c = t >> 29; }
   r.l[8] = a.l[8] + c;
+  ZKR29_EXPECT(r.l[8] >= c);
   return r;
 }
 // M r written so that it dominates a [U, M - 1] value limb by limb (zkwg_fq29.h fq29_negc_make, with r's limbs)
@@ -120,6 +199,10 @@ constexpr Fr29C fr29_negc_make() {
 template <int M, int U>
 ZK_HD Fr29 fr29_sub(const Fr29& a, const Fr29& b) {
   constexpr Fr29C c = fr29_negc_make<M, U>();
+#if !defined(__HIP_DEVICE_COMPILE__) && defined(ZKWG_FR29_CHECK)
+  ZKR29_EXPECT(zkr29_big_cmp(zkr29_big(b.l), zkr29_big_kr(M - 1)) <= 0);     // b <= (M - 1) r ...
+  for (int i = 0; i < 9; ++i) { ZKR29_EXPECT(c.l[i] >= b.l[i]); ZKR29_EXPECT(a.l[i] + (c.l[i] - b.l[i]) >= a.l[i]); }   // ... limb by limb, no wrap
+#endif
   Fr29 r;
   r.l[0] = a.l[0] + (c.l[0] - b.l[0]); r.l[1] = a.l[1] + (c.l[1] - b.l[1]); r.l[2] = a.l[2] + (c.l[2] - b.l[2]);
   r.l[3] = a.l[3] + (c.l[3] - b.l[3]); r.l[4] = a.l[4] + (c.l[4] - b.l[4]); r.l[5] = a.l[5] + (c.l[5] - b.l[5]);
@@ -129,6 +212,7 @@ ZK_HD Fr29 fr29_sub(const Fr29& a, const Fr29& b) {
 // any limb form with value < 2^256 packed into 4 x 64-bit words (NOT reduced: the work buffers of the transforms hold such words)
 ZK_HD Fr fr29_pack(const Fr29& x) {
   const Fr29 t = fr29_norm(x);
+  ZKR29_EXPECT(t.l[8] < (1u << 24));              // value < 2^256
   u64 w[4] = {0, 0, 0, 0};
 #pragma unroll
   for (int i = 0; i < 9; ++i) {
@@ -138,9 +222,12 @@ ZK_HD Fr fr29_pack(const Fr29& x) {
   }
   return Fr{{w[0], w[1], w[2], w[3]}};
 }
-// canonical words of a value < V r (V <= 63)
+// canonical words of a value < V r (V <= 64: subtracts 32 r, 16 r, .., r where below V)
 template <int V>
 ZK_HD Fr fr29_to_fr_v(const Fr29& a) {
+#if !defined(__HIP_DEVICE_COMPILE__) && defined(ZKWG_FR29_CHECK)
+  ZKR29_EXPECT(zkr29_below_kr(a.l, V));
+#endif
   Fr29 n = fr29_norm(a);
 #pragma unroll
   for (int s = 5; s >= 0; --s) {
@@ -172,5 +259,6 @@ ZK_HD Fr fr29_to_fr_v(const Fr29& a) {
     w[k] |= (u64)n.l[i] << s;
     if (s > 64 - 29 && k + 1 < 4) w[k + 1] |= (u64)n.l[i] >> (64 - s);
   }
+  ZKR29_EXPECT(!fr_geq(Fr{{w[0], w[1], w[2], w[3]}}, fr_p()) && n.l[8] < (1u << 24));    // canonical
   return Fr{{w[0], w[1], w[2], w[3]}};
 }

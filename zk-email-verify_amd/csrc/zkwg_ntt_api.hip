@@ -4,7 +4,7 @@
 #include <string>
 #include <vector>
 #include "../../include/zkwg.h"
-#include "zkwg_fr.h"
+#include "zkwg_ntt_core.h"
 
 extern "C" int zk_ntt_launch(int dit, const Fr* src, u64 src_es, u64 src_ps, u64 valid, int src_lazy, void* work, Fr* out, const Fr* tw, const Fr* scale,
                              const Fr* uni_host, u32 L, u32 n_polys, u32 inv, hipStream_t st);
@@ -22,16 +22,6 @@ struct zkwg_ntt {
   Fr ninv_m;      // 1 / n
 };
 
-static Fr pow_m(Fr base_m, const u64 e[4]) {   // Montgomery in / out
-  Fr acc = fr_R();
-  for (int i = 255; i >= 0; --i) {
-    acc = fr_mont_mul(acc, acc);
-    if ((e[i >> 6] >> (i & 63)) & 1) acc = fr_mont_mul(acc, base_m);
-  }
-  return acc;
-}
-static u32 bitrev_host(u32 x, u32 bits) { u32 r = 0; for (u32 i = 0; i < bits; ++i) r |= ((x >> i) & 1u) << (bits - 1u - i); return r; }
-
 extern "C" {
 
 int zkwg_ntt_create(int device, uint32_t log2_n, zkwg_ntt_t** out) {
@@ -39,27 +29,8 @@ int zkwg_ntt_create(int device, uint32_t log2_n, zkwg_ntt_t** out) {
   try {
     zkwg_ntt* p = new zkwg_ntt();
     p->device = device; p->L = log2_n; p->n = 1ull << log2_n; p->d_tw = p->d_scale = nullptr;
-    // ffjavascript F1Field: s = 28, t = (r - 1) >> 28, w[28] = 5^t, w[i] = w[i+1]^2, shift = 5^2
-    const u64 r1[4] = {ZK_P0 - 1, ZK_P1, ZK_P2, ZK_P3};
-    u64 t[4];
-    for (int i = 0; i < 4; ++i) t[i] = (r1[i] >> 28) | (i < 3 ? r1[i + 1] << 36 : 0);
-    const Fr five_m = fr_to_mont(fr_from_u64(5));
-    Fr w = pow_m(five_m, t);                                   // w[28]
-    Fr wL1 = w;                                                // w[L + 1] (L < 28)
-    for (u32 i = 28; i > log2_n; --i) { if (i == log2_n + 1) wL1 = w; w = fr_mont_mul(w, w); }
-    const Fr inc = log2_n == 28 ? fr_to_mont(fr_from_u64(25)) : wL1;
-    std::vector<Fr> tw(p->n), sc(p->n);
-    Fr acc = fr_R();
-    for (u64 k = 0; k < p->n; ++k) { tw[k] = acc; acc = fr_mont_mul(acc, w); }
-    if (!fr_eq(acc, fr_R()) || !fr_eq(tw[p->n / 2], fr_neg(fr_R()))) { delete p; return ZKWG_RC_BAD_CONFIG; }   // w^n = 1, w^(n/2) = -1
-    const u64 e2[4] = {ZK_P0 - 2, ZK_P1, ZK_P2, ZK_P3};
-    p->ninv_m = pow_m(fr_to_mont(fr_from_u64(p->n)), e2);
-    acc = p->ninv_m;
-    for (u64 i = 0; i < p->n; ++i) { sc[bitrev_host((u32)i, log2_n)] = acc; acc = fr_mont_mul(acc, inc); }
-    // 2^256 form -> 2^261 form: times 32
-    const Fr m32 = fr_to_mont(fr_from_u64(32));
-    for (u64 k = 0; k < p->n; ++k) { tw[k] = fr_mont_mul(tw[k], m32); sc[k] = fr_mont_mul(sc[k], m32); }
-    p->ninv_m = fr_mont_mul(p->ninv_m, m32);
+    std::vector<Fr> tw, sc;
+    if (!zk_ntt_tables(log2_n, tw, sc, p->ninv_m)) { delete p; return ZKWG_RC_BAD_CONFIG; }   // (zkwg_ntt_core.h: shared with the host mirror)
     if (device >= 0) {
       if (hipSetDevice(device) != hipSuccess) { delete p; return ZKWG_RC_NO_DEVICE; }
       if (hipMalloc((void**)&p->d_tw, p->n * sizeof(Fr)) != hipSuccess || hipMalloc((void**)&p->d_scale, p->n * sizeof(Fr)) != hipSuccess ||
