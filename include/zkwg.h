@@ -108,7 +108,9 @@ enum zkwg_input_field {
 /* Per-email status: circom_runtime exception codes. */
 enum zkwg_status {
   ZKWG_OK = 0,
-  ZKWG_ERR_ASSERT_FAILED = 4 /* a `===` / assert failed: "Assert Failed" */
+  ZKWG_ERR_ASSERT_FAILED = 4, /* a `===` / assert failed: "Assert Failed" */
+  ZKWG_ERR_WITNESS_NOT_REDUCED = 7 /* zkwg_prover_prove_witnesses: a witness value is not below the group order r (no circom_runtime
+                                      code: those are 1 .. 6); such a witness gets no proof */
 };
 
 /* API return codes (negative = misuse / runtime failure). */
@@ -389,7 +391,8 @@ int zkwg_check_constraints(zkwg_r1cs_t* r, const uint8_t* witness, uint64_t n, u
  * B, then C -- `abc_stride` (>= 96 * nConstraints) bytes apart.  A witness in Montgomery form
  * (zkwg_expand_montgomery_device; pass montgomery = 1) yields evaluations in Montgomery form, a standard-form witness
  * (montgomery = 0) standard-form ones; nothing is converted or copied to the host.  The flag only selects a shortcut
- * (a Montgomery-form 0 or 1 needs no product); the arithmetic is the same.  NTT / MSM are not part of this library. */
+ * (a Montgomery-form 0 or 1 needs no product); the arithmetic is the same.  The transforms and the sums that follow are the prover
+ * stages 2 and 3 below (zkwg_ntt_*, zkwg_msm_*); zkwg_prover_* runs all of them. */
 int zkwg_r1cs_evaluate_device(zkwg_r1cs_t* r, const void* d_witness, uint64_t n, uint64_t stride, int montgomery,
                               void* d_abc, uint64_t abc_stride, void* hip_stream);
 
@@ -534,6 +537,37 @@ uint32_t zkwg_prover_contexts(const zkwg_prover_t* p);
 int zkwg_prover_prove_prepared(zkwg_prover_t* p, const void* d_in, uint64_t n, const void* d_scratch, const uint64_t* indices, uint64_t n_idx,
                                const uint8_t* blinding, uint8_t* out_proofs);
 int zkwg_prover_prove_batch(zkwg_prover_t* p, const uint8_t* packed, uint64_t n, const uint8_t* blinding, int32_t* status, uint8_t* out_proofs);
+
+/* ---- `groth16.prove(zkey, wtns)` for ANY BN254 groth16 key: the prover of witnesses (no circuit handle) --------------------------------
+ * zkwg_prover_create_wtns takes the .zkey and nothing else: section 4 becomes a row table on the device (csrc/zkwg_zkey_core.h), the
+ * bases of sections 5-9 the plans of the five sums, `slots` proofs are in flight through the same rolling contexts as above.  Refused
+ * with ZKWG_RC_BAD_CONFIG: a file that is not a BN254 groth16 key or whose section sizes disagree with its header, a coefficient with
+ * wire >= nVars, row >= domainSize, matrix > 1 or value >= r, a row of more than 2^20 terms, nVars >= 2^31, and B1 / B2 base sets whose
+ * points at infinity sit at different wires (the two sums share one classification of the witness).
+ * zkwg_prover_prove_witnesses: n witnesses in host memory, `stride` (>= 32 * zkwg_prover_witness_len) bytes apart, each nVars 32-byte
+ * little-endian standard-form values -- section 2 of a `.wtns` file (zkwg_wtns_parse tells where it starts); blinding = n x (r | s);
+ * out_proofs = n x 256 bytes in the form of zkwg_prover_prove_batch.  status[i] = 0, or ZKWG_ERR_WITNESS_NOT_REDUCED when a value of
+ * witness i is >= r (found on the device over all nVars values; its proof bytes are zero, nothing of it reaches the sums).  A witness
+ * that violates a constraint still gets a proof, as from snarkjs: the verifier rejects it.  The witnesses of a series are copied through
+ * pinned staging on the series' own stream, so the copy of one series overlaps the sums of another.
+ * zkwg_prover_prove_witnesses_device: the same for witnesses already in device memory (16-byte aligned, stride a multiple of 16).
+ * A.w | B.w | C.w (C.w = A.w o B.w, snarkjs' buildABC1) come from zk_zkey_abc (csrc/zkwg_kernels_zkey.hip); zkwg_prover_abc_device runs
+ * that stage alone: n records of 3 * zkwg_prover_rows values, Montgomery form, abc_stride (>= 96 * rows, multiple of 32) bytes apart.
+ * The email entry points (zkwg_prover_prove_prepared / _batch) return ZKWG_RC_BAD_ARG on such a prover, and these on a handle prover.
+ * zkwg_zkey_check: the checks of creation on the host alone (no device). */
+int zkwg_prover_create_wtns(int device, const uint8_t* zkey, uint64_t zkey_len, uint32_t slots, zkwg_prover_t** out);
+uint64_t zkwg_prover_witness_len(const zkwg_prover_t* p);   /* nVars of the key */
+uint32_t zkwg_prover_num_public(const zkwg_prover_t* p);
+uint64_t zkwg_prover_rows(const zkwg_prover_t* p);          /* rows of A (the nPublic + 1 public rows included) */
+int zkwg_prover_prove_witnesses(zkwg_prover_t* p, const uint8_t* witnesses, uint64_t stride, uint64_t n, const uint8_t* blinding, int32_t* status,
+                                uint8_t* out_proofs);
+int zkwg_prover_prove_witnesses_device(zkwg_prover_t* p, const void* d_witnesses, uint64_t stride, uint64_t n, const uint8_t* blinding, int32_t* status,
+                                       uint8_t* out_proofs);
+int zkwg_prover_abc_device(zkwg_prover_t* p, const void* d_witnesses, uint64_t stride, uint64_t n, void* d_abc, uint64_t abc_stride, void* hip_stream);
+/* `.wtns` (magic "wtns", version 2; section 1: n8 = 32, the prime r, nWitness; section 2: 32 * nWitness bytes; either order):
+ * *values_offset = where section 2's values start.  ZKWG_RC_BAD_CONFIG for anything else. */
+int zkwg_wtns_parse(const uint8_t* wtns, uint64_t len, uint64_t* n_witness, uint64_t* values_offset);
+int zkwg_zkey_check(const uint8_t* zkey, uint64_t zkey_len, uint64_t* n_vars, uint32_t* n_public, uint64_t* n_rows);
 
 /* The same prover stage without a 32-byte witness in between: the constraint system `r1cs` (its wires = the handle's
  * witness layout: built-in, `.sym`, or -- since ABI 3 -- a fully numbered handle of zkwg_circuit_create_full, whose system is

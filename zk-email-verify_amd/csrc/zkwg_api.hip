@@ -244,6 +244,7 @@ const char* zkwg_strerror(int rc) {
     case 3: return "Signal already set";
     case 5: return "Not enough memory";
     case 6: return "Input signal array access exceeds the size";
+    case ZKWG_ERR_WITNESS_NOT_REDUCED: return "zkwg: a witness value is not below the field order";
     case ZKWG_RC_BAD_CONFIG: return "zkwg: unsupported circuit configuration";
     case ZKWG_RC_BAD_ARG: return "zkwg: bad argument";
     case ZKWG_RC_NO_DEVICE: return "zkwg: no HIP device (layout-only handle or HIP unavailable)";

@@ -20,6 +20,7 @@
 #include <vector>
 #include "../../include/zkwg.h"
 #include "zkwg_fq.h"
+#include "zkwg_zkey_core.h"
 
 struct ZkProveCtx {
   hipStream_t st_h = nullptr, st_w = nullptr, st_g = nullptr;
@@ -27,13 +28,19 @@ struct ZkProveCtx {
   uint8_t *wit = nullptr, *abc = nullptr, *h = nullptr, *ntt = nullptr, *work_h = nullptr, *work_w = nullptr, *work_g = nullptr, *sums = nullptr;
   uint8_t* lists[3] = {nullptr, nullptr, nullptr};
   uint8_t* host_sums = nullptr;        // pinned: E x 5 x 256
+  // a prover of witnesses (zkwg_prover_create_wtns): the host path's pinned staging copy of E witnesses, and the "value not reduced" flags
+  uint8_t* stage = nullptr;
+  int *flags = nullptr, *host_flags = nullptr;
   uint64_t first = 0, count = 0;       // positions [first, first + count) of the call's index list are in flight here
   bool busy = false;
 };
 struct zkwg_prover {
-  zkwg_circuit_t* c;
+  zkwg_circuit_t* c;                   // nullptr: made from the zkey alone, proves witnesses (zkwg_prover_create_wtns)
   int device;
   uint64_t n_rows, n_public, W;
+  uint64_t wb = 0, ab = 0;             // bytes of one witness / of one record A.w | B.w | C.w in the contexts
+  ZkZkeyDev zt{};                      // the key's own rows on the device (c == nullptr)
+  void* zt_mem[5] = {nullptr, nullptr, nullptr, nullptr, nullptr};
   uint32_t power, E;
   int c_from_ab = 0;                   // 1: the attached system has no C rows (a zkey's section 4): C.w = A.w o B.w (zkwg_prover_create_zkey)
   zkwg_ntt_t* ntt = nullptr;
@@ -42,6 +49,8 @@ struct zkwg_prover {
   std::vector<ZkProveCtx> ctx;
 };
 void zk_abc_c_from_ab_launch(void* d_abc, uint64_t abc_stride, uint64_t n_rows, uint32_t n_emails, hipStream_t st);      // zkwg_kernels_handoff.hip
+int zk_zkey_abc_launch(const ZkZkeyDev& T, const void* d_wit, u64 stride, u32 count, void* d_abc, u64 abc_stride, hipStream_t st);   // zkwg_kernels_zkey.hip
+int zk_zkey_range_launch(void* d_wit, u64 stride, u64 n_vars, u32 count, int* d_flags, hipStream_t st);
 
 static void prover_free(zkwg_prover* p) {
   if (!p) return;
@@ -51,7 +60,11 @@ static void prover_free(zkwg_prover* p) {
     for (hipEvent_t ev : {s.ev_wit, s.ev_lists, s.ev_w, s.ev_g, s.ev_done}) if (ev) hipEventDestroy(ev);
     for (uint8_t* q : {s.wit, s.abc, s.h, s.ntt, s.work_h, s.work_w, s.work_g, s.sums, s.lists[0], s.lists[1], s.lists[2]}) if (q) hipFree(q);
     if (s.host_sums) hipHostFree(s.host_sums);
+    if (s.stage) hipHostFree(s.stage);
+    if (s.host_flags) hipHostFree(s.host_flags);
+    if (s.flags) hipFree(s.flags);
   }
+  for (void* q : p->zt_mem) if (q) hipFree(q);
   zkwg_msm_destroy(p->ma); zkwg_msm_destroy(p->mb1); zkwg_msm_destroy(p->mb2); zkwg_msm_destroy(p->mc); zkwg_msm_destroy(p->mh);
   zkwg_ntt_destroy(p->ntt);
   delete p;
@@ -66,9 +79,9 @@ static void prover_shape(uint32_t slots, uint32_t& n_ctx, uint32_t& E) {
 }
 
 static int prover_new(zkwg_circuit_t* c, int device, uint64_t n_rows, const zkwg_proving_key* key, uint32_t slots, int c_from_ab, zkwg_prover_t** out) {
-  const uint64_t W = zkwg_witness_len(c), n = 1ull << key->log2_domain;
+  const uint64_t W = c ? zkwg_witness_len(c) : key->n_wires, n = 1ull << key->log2_domain;
   if (key->n_wires != W || key->n_public + 1 >= W || n_rows > n || key->log2_domain > 28) return ZKWG_RC_BAD_CONFIG;
-  if (zkwg_abc_bytes(c) != 96 * n_rows) return ZKWG_RC_BAD_CONFIG;
+  if (c && zkwg_abc_bytes(c) != 96 * n_rows) return ZKWG_RC_BAD_CONFIG;
   if (hipSetDevice(device) != hipSuccess) return ZKWG_RC_HIP_ERROR;
   zkwg_prover* p = new zkwg_prover();
   p->c = c; p->device = device; p->n_rows = n_rows; p->n_public = key->n_public; p->W = W; p->power = (uint32_t)key->log2_domain; p->c_from_ab = c_from_ab;
@@ -79,7 +92,8 @@ static int prover_new(zkwg_circuit_t* c, int device, uint64_t n_rows, const zkwg
   const uint64_t E = p->E;
   // What the contexts will need is set aside BEFORE the tables are sized (the tables took what was free and the slots then
   // failed): a table's K copies are only made when they fit beside it, otherwise that plan keeps the classic layout.
-  const uint64_t wb = zkwg_witness_bytes(c), ab = zkwg_abc_bytes(c), hb = 32ull << p->power;
+  const uint64_t wb = c ? zkwg_witness_bytes(c) : 32 * W, ab = 96 * n_rows, hb = 32ull << p->power;
+  p->wb = wb; p->ab = ab;
   // (work buffers: bounded by the witness-shaped G2 plan at window 13 and the H plan at window 16 -- estimated with their own formulas below)
   size_t free_b = 0, total_b = 0;
   if (hipMemGetInfo(&free_b, &total_b) != hipSuccess) { free_b = 0; (void)hipGetLastError(); }
@@ -123,19 +137,37 @@ static int prover_new(zkwg_circuit_t* c, int device, uint64_t n_rows, const zkwg
          hipMalloc((void**)&s.sums, E * 5 * 256) == hipSuccess && hipMalloc((void**)&s.lists[0], zkwg_msm_lists_bytes(p->ma, E)) == hipSuccess &&
          hipMalloc((void**)&s.lists[1], zkwg_msm_lists_bytes(p->mb1, E)) == hipSuccess && hipMalloc((void**)&s.lists[2], zkwg_msm_lists_bytes(p->mc, E)) == hipSuccess &&
          hipHostMalloc((void**)&s.host_sums, E * 5 * 256, hipHostMallocDefault) == hipSuccess;
+    if (!c) ok = ok && hipMalloc((void**)&s.flags, E * 4) == hipSuccess && hipHostMalloc((void**)&s.host_flags, E * 4, hipHostMallocDefault) == hipSuccess;
     if (!ok) { prover_free(p); (void)hipGetLastError(); return ZKWG_RC_OOM; }
   }
   *out = p;
   return ZKWG_RC_OK;
 }
 
-// one series for the emails indices[first .. first + count) on context s (nothing synchronised)
+// one series on context s (nothing synchronised).  A handle prover: the emails indices[first .. first + count) of the prepared batch
+// (d_in, n, d_scratch).  A prover of witnesses (p->c == nullptr): the witnesses [first, first + count) of the caller's array d_in (`n` = their
+// stride in bytes; in host memory if `d_scratch` is nullptr, else in device memory) are copied into the context on stream h -- the host path
+// through the context's pinned staging area, so that the copy of this series overlaps the sums of the others --, checked for values >= r
+// (zk_zkey_range: such a witness is flagged and zeroed in the copy) and evaluated by zk_zkey_abc.  Everything after ev_wit is the same code.
 static int prover_enqueue(zkwg_prover* p, ZkProveCtx& s, const void* d_in, uint64_t n, const void* d_scratch, const uint64_t* indices, uint64_t first, uint64_t count) {
   zkwg_circuit_t* c = p->c;
-  const uint64_t wb = zkwg_witness_bytes(c), ab = zkwg_abc_bytes(c), hb = 32ull << p->power;
+  const uint64_t wb = p->wb, ab = p->ab, hb = 32ull << p->power;
   int rc = ZKWG_RC_OK;
+  if (!c) {
+    const uint64_t stride = n, row = 32 * p->W;
+    const uint8_t* src = (const uint8_t*)d_in + first * stride;
+    if (!d_scratch) {
+      if (!s.stage && hipHostMalloc((void**)&s.stage, p->E * wb, hipHostMallocDefault) != hipSuccess) { (void)hipGetLastError(); return ZKWG_RC_OOM; }
+      for (uint64_t j = 0; j < count; ++j) memcpy(s.stage + j * wb, src + j * stride, row);
+      if (hipMemcpyAsync(s.wit, s.stage, count * wb, hipMemcpyHostToDevice, s.st_h) != hipSuccess) return ZKWG_RC_HIP_ERROR;
+    } else if (hipMemcpy2DAsync(s.wit, wb, src, stride, row, count, hipMemcpyDeviceToDevice, s.st_h) != hipSuccess) {
+      return ZKWG_RC_HIP_ERROR;
+    }
+    if (zk_zkey_range_launch(s.wit, wb, p->W, (u32)count, s.flags, s.st_h) != 0) return ZKWG_RC_HIP_ERROR;
+    if (zk_zkey_abc_launch(p->zt, s.wit, wb, (u32)count, s.abc, ab, s.st_h) != 0) return ZKWG_RC_HIP_ERROR;
+  }
   // witnesses and A.w | B.w | C.w: one launch per run of consecutive emails
-  for (uint64_t j = 0; j < count && rc == ZKWG_RC_OK;) {
+  for (uint64_t j = 0; c && j < count && rc == ZKWG_RC_OK;) {
     uint64_t run = 1;
     while (j + run < count && indices[first + j + run] == indices[first + j] + run) ++run;
     if (indices[first + j] + run > n) return ZKWG_RC_BAD_ARG;
@@ -166,13 +198,14 @@ static int prover_enqueue(zkwg_prover* p, ZkProveCtx& s, const void* d_in, uint6
       hipStreamWaitEvent(s.st_h, s.ev_g, 0) != hipSuccess)
     return ZKWG_RC_HIP_ERROR;
   // (sums: five arrays of E accumulators, array k at sums + k E 256)
+  if (!c && hipMemcpyAsync(s.host_flags, s.flags, 4 * count, hipMemcpyDeviceToHost, s.st_h) != hipSuccess) return ZKWG_RC_HIP_ERROR;
   if (hipMemcpyAsync(s.host_sums, s.sums, p->E * 5 * 256, hipMemcpyDeviceToHost, s.st_h) != hipSuccess || hipEventRecord(s.ev_done, s.st_h) != hipSuccess)
     return ZKWG_RC_HIP_ERROR;
   s.first = first; s.count = count; s.busy = true;
   return ZKWG_RC_OK;
 }
 // wait for context s, assemble its proofs
-static int prover_finish(zkwg_prover* p, ZkProveCtx& s, const uint8_t* blinding, uint8_t* out_proofs) {
+static int prover_finish(zkwg_prover* p, ZkProveCtx& s, const uint8_t* blinding, uint8_t* out_proofs, int32_t* status = nullptr) {
   if (!s.busy) return ZKWG_RC_OK;
   s.busy = false;
   if (hipEventSynchronize(s.ev_done) != hipSuccess) return ZKWG_RC_HIP_ERROR;
@@ -182,6 +215,8 @@ static int prover_finish(zkwg_prover* p, ZkProveCtx& s, const uint8_t* blinding,
     // sum k of email j: array k holds E accumulators of 256 bytes (G1 uses the first 128)
     for (int k = 0; k < 5; ++k) zkwg_msm_finish_host(k == 2 ? 2 : 1, s.host_sums + (uint64_t)k * p->E * 256 + j * (k == 2 ? 256 : 128), 1, pts[k]);
     uint8_t* o = out_proofs + 256 * (s.first + j);
+    if (status) status[s.first + j] = s.host_flags[j] ? ZKWG_ERR_WITNESS_NOT_REDUCED : ZKWG_OK;
+    if (status && s.host_flags[j]) { memset(o, 0, 256); continue; }       // (its copy was zeroed before the sums: no proof)
     const uint8_t* bl = blinding + 64 * (s.first + j);
     rc = zkwg_groth16_assemble(pts[0], pts[1], pts[2], pts[3], pts[4], p->alpha1, p->beta1, p->beta2, p->delta1, p->delta2, bl, bl + 32, o, o + 64, o + 192);
   }
@@ -207,67 +242,25 @@ int zkwg_prover_create(zkwg_circuit_t* c, int device, const uint8_t* r1cs, uint6
 // to the handle like any other system (zkwg_circuit_attach_r1cs: A.w and B.w then come straight from the compact image), and every
 // series computes C.w = A.w o B.w before the transforms (zk_abc_c_from_ab).  Container layout restated from snarkjs [EXT]:
 // zkwg/zkey.py has the field-by-field description.
-static bool zkey_sections(const uint8_t* z, uint64_t len, uint64_t (&off)[11], uint64_t (&size)[11]) {
-  for (int i = 0; i < 11; ++i) off[i] = size[i] = 0;
-  if (len < 12 || memcmp(z, "zkey", 4) != 0) return false;
-  uint32_t version, nsec;
-  memcpy(&version, z + 4, 4); memcpy(&nsec, z + 8, 4);
-  if (version != 1) return false;
-  uint64_t pos = 12;
-  for (uint32_t i = 0; i < nsec; ++i) {
-    if (pos + 12 > len) return false;
-    uint32_t id; uint64_t sz;
-    memcpy(&id, z + pos, 4); memcpy(&sz, z + pos + 4, 8);
-    pos += 12;
-    if (sz > len - pos) return false;
-    if (id >= 1 && id <= 10) { off[id] = pos; size[id] = sz; }
-    pos += sz;
-  }
-  return true;
-}
 int zkwg_prover_create_zkey(zkwg_circuit_t* c, int device, const uint8_t* zkey, uint64_t zkey_len, uint32_t slots, zkwg_prover_t** out) {
   if (!c || !zkey || !out || slots == 0 || slots > 256) return ZKWG_RC_BAD_ARG;
   if (device < 0) return ZKWG_RC_NO_DEVICE;
-  uint64_t off[11], size[11];
-  if (!zkey_sections(zkey, zkey_len, off, size)) return ZKWG_RC_BAD_CONFIG;
-  for (int need : {1, 2, 4, 5, 6, 7, 8, 9}) if (!off[need]) return ZKWG_RC_BAD_CONFIG;
-  uint32_t protocol;
-  memcpy(&protocol, zkey + off[1], 4);
-  if (size[1] < 4 || protocol != 1) return ZKWG_RC_BAD_CONFIG;                     // groth16
-  // header: n8q, q, n8r, r, nVars, nPublic, domainSize, alpha1, beta1, beta2, gamma2, delta1, delta2
-  const uint8_t* h = zkey + off[2];
-  if (size[2] < 4 + 32 + 4 + 32 + 12 + 64 + 64 + 128 + 128 + 64 + 128) return ZKWG_RC_BAD_CONFIG;
-  uint32_t n8q, n8r, n_vars, n_public, domain;
-  memcpy(&n8q, h, 4); memcpy(&n8r, h + 36, 4);
-  const Fq q = fq_p(); const Fr r = fr_p();
-  if (n8q != 32 || n8r != 32 || memcmp(h + 4, q.l, 32) != 0 || memcmp(h + 40, r.l, 32) != 0) return ZKWG_RC_BAD_CONFIG;      // BN254
-  memcpy(&n_vars, h + 72, 4); memcpy(&n_public, h + 76, 4); memcpy(&domain, h + 80, 4);
-  if (domain == 0 || (domain & (domain - 1)) || n_public + 1 >= n_vars) return ZKWG_RC_BAD_CONFIG;
-  uint32_t power = 0;
-  while ((1u << power) < domain) ++power;
-  if (size[5] != 64ull * n_vars || size[6] != 64ull * n_vars || size[7] != 128ull * n_vars || size[8] != 64ull * (n_vars - n_public - 1) || size[9] != 64ull * domain)
-    return ZKWG_RC_BAD_CONFIG;
+  // (the section walker, the header reader and the range checks of section 4: zkwg_zkey_core.h, shared with zkwg_prover_create_wtns)
+  ZkZkeyHeader H;
+  int rc0 = zk_zkey_header(zkey, zkey_len, H);
+  if (rc0 != ZKWG_RC_OK) return rc0;
+  const uint64_t (&off)[11] = H.off;
+  const uint32_t n_vars = H.n_vars, n_public = H.n_public;
+  const Fr r = fr_p();
   zkwg_proving_key key;
-  memset(&key, 0, sizeof key);
-  key.n_wires = n_vars; key.n_public = n_public; key.log2_domain = power;
-  key.a = zkey + off[5]; key.b1 = zkey + off[6]; key.b2 = zkey + off[7]; key.c = zkey + off[8]; key.h = zkey + off[9]; key.bases_on_device = 0;
-  const uint8_t* pts = h + 84;
-  memcpy(key.alpha1, pts, 64); memcpy(key.beta1, pts + 64, 64); memcpy(key.beta2, pts + 128, 128);
-  memcpy(key.delta1, pts + 384, 64); memcpy(key.delta2, pts + 448, 128);                           // (gamma2 sits between beta2 and delta1)
+  zk_zkey_key(zkey, H, key);
   // section 4 -> rows of A and B
-  if (size[4] < 4) return ZKWG_RC_BAD_CONFIG;
   uint32_t n_coef;
   memcpy(&n_coef, zkey + off[4], 4);
-  if (size[4] != 4 + 44ull * n_coef) return ZKWG_RC_BAD_CONFIG;
   const uint8_t* cf = zkey + off[4] + 4;
   uint64_t n_rows = 0;
-  for (uint32_t i = 0; i < n_coef; ++i) {
-    uint32_t m, row, wire;
-    memcpy(&m, cf + 44ull * i, 4); memcpy(&row, cf + 44ull * i + 4, 4); memcpy(&wire, cf + 44ull * i + 8, 4);
-    if (m > 1 || wire >= n_vars || row >= domain) return ZKWG_RC_BAD_CONFIG;
-    n_rows = std::max<uint64_t>(n_rows, (uint64_t)row + 1);
-  }
-  if (n_rows == 0) return ZKWG_RC_BAD_CONFIG;
+  rc0 = zk_zkey_coef_ranges(zkey, H, n_rows);
+  if (rc0 != ZKWG_RC_OK) return rc0;
   std::vector<uint32_t> cnt(2 * n_rows + 1, 0);                      // terms of A row i at 2 i, of B row i at 2 i + 1
   for (uint32_t i = 0; i < n_coef; ++i) {
     uint32_t m, row;
@@ -326,13 +319,92 @@ int zkwg_prover_create_zkey(zkwg_circuit_t* c, int device, const uint8_t* zkey, 
   file.clear(); file.shrink_to_fit();
   return prover_new(c, device, n_rows, &key, slots, 1, out);
 }
+// The prover of WITNESSES: made from the zkey alone, no circuit handle -- `groth16.prove(zkey, wtns)` for any BN254 groth16 key and the
+// witness its own calculator wrote.  Section 4 becomes the row table of zkwg_zkey_core.h on the device; zk_zkey_abc evaluates it.
+int zkwg_prover_create_wtns(int device, const uint8_t* zkey, uint64_t zkey_len, uint32_t slots, zkwg_prover_t** out) {
+  if (!zkey || !out || slots == 0 || slots > 256) return ZKWG_RC_BAD_ARG;
+  if (device < 0) return ZKWG_RC_NO_DEVICE;
+  ZkZkeyHeader H;
+  int rc = zk_zkey_header(zkey, zkey_len, H);
+  if (rc != ZKWG_RC_OK) return rc;
+  ZkZkeyHost T;
+  rc = zk_zkey_rows(zkey, H, T);
+  if (rc == ZKWG_RC_OK) rc = zk_zkey_b_bitmaps(zkey, H);       // (the sums b1 and b2 share one classification of the witness)
+  if (rc != ZKWG_RC_OK) return rc;
+  zkwg_proving_key key;
+  zk_zkey_key(zkey, H, key);
+  zkwg_prover* p = nullptr;
+  rc = prover_new(nullptr, device, T.n_rows, &key, slots, 0, &p);
+  if (rc != ZKWG_RC_OK) return rc;
+  const void* src[5] = {T.rows.data(), T.unit.data(), T.gwire.data(), T.gcoef.data(), T.order.data()};
+  const uint64_t bytes[5] = {T.rows.size() * sizeof(ZkZkeyRow), T.unit.size() * 4, T.gwire.size() * 4, T.gcoef.size() * 32, T.order.size() * 4};
+  for (int k = 0; k < 5; ++k) {
+    if (hipMalloc(&p->zt_mem[k], bytes[k] ? bytes[k] : 16) != hipSuccess) { prover_free(p); (void)hipGetLastError(); return ZKWG_RC_OOM; }
+    if (bytes[k] && hipMemcpy(p->zt_mem[k], src[k], bytes[k], hipMemcpyHostToDevice) != hipSuccess) { prover_free(p); return ZKWG_RC_HIP_ERROR; }
+  }
+  p->zt = ZkZkeyDev{(const ZkZkeyRow*)p->zt_mem[0], (const u32*)p->zt_mem[1], (const u32*)p->zt_mem[2], (const Fr*)p->zt_mem[3], (const u32*)p->zt_mem[4],
+                    fr29_from_fr(T.k1), T.n_rows, T.n_long};
+  *out = p;
+  return ZKWG_RC_OK;
+}
+uint64_t zkwg_prover_witness_len(const zkwg_prover_t* p) { return p ? p->W : 0; }
+uint32_t zkwg_prover_num_public(const zkwg_prover_t* p) { return p ? (uint32_t)p->n_public : 0; }
+uint64_t zkwg_prover_rows(const zkwg_prover_t* p) { return p ? p->n_rows : 0; }
+int zkwg_wtns_parse(const uint8_t* wtns, uint64_t len, uint64_t* n_witness, uint64_t* values_offset) { return zk_wtns_parse(wtns, len, n_witness, values_offset); }
+int zkwg_zkey_check(const uint8_t* zkey, uint64_t zkey_len, uint64_t* n_vars, uint32_t* n_public, uint64_t* n_rows) {
+  if (!zkey) return ZKWG_RC_BAD_ARG;
+  ZkZkeyHeader H;
+  int rc = zk_zkey_header(zkey, zkey_len, H);
+  if (rc != ZKWG_RC_OK) return rc;
+  ZkZkeyHost T;
+  rc = zk_zkey_rows(zkey, H, T);
+  if (rc == ZKWG_RC_OK) rc = zk_zkey_b_bitmaps(zkey, H);
+  if (rc != ZKWG_RC_OK) return rc;
+  if (n_vars) *n_vars = H.n_vars;
+  if (n_public) *n_public = H.n_public;
+  if (n_rows) *n_rows = T.n_rows;
+  return ZKWG_RC_OK;
+}
+// zk_zkey_abc alone, on device-resident witnesses (what a series runs first; tests and tools/bench_prove_wtns.py)
+int zkwg_prover_abc_device(zkwg_prover_t* p, const void* d_witnesses, uint64_t stride, uint64_t n, void* d_abc, uint64_t abc_stride, void* hip_stream) {
+  if (!p || p->c || !d_witnesses || !d_abc || stride < 32 * p->W || (stride & 15) || ((uintptr_t)d_witnesses & 15) || abc_stride < 96 * p->n_rows || (abc_stride & 31) ||
+      n > 0xffffu * 2) return ZKWG_RC_BAD_ARG;
+  if (hipSetDevice(p->device) != hipSuccess) return ZKWG_RC_HIP_ERROR;
+  return zk_zkey_abc_launch(p->zt, d_witnesses, stride, (u32)n, d_abc, abc_stride, (hipStream_t)hip_stream) == 0 ? ZKWG_RC_OK : ZKWG_RC_HIP_ERROR;
+}
+static int prove_witnesses(zkwg_prover* p, const void* wit, uint64_t stride, uint64_t n, bool on_device, const uint8_t* blinding, int32_t* status, uint8_t* out_proofs) {
+  if (!p || p->c || !wit || !blinding || !status || !out_proofs || stride < 32 * p->W) return ZKWG_RC_BAD_ARG;
+  if (on_device && ((stride & 15) || ((uintptr_t)wit & 15))) return ZKWG_RC_BAD_ARG;
+  if (n == 0) return ZKWG_RC_OK;
+  if (hipSetDevice(p->device) != hipSuccess) return ZKWG_RC_HIP_ERROR;
+  int rc = ZKWG_RC_OK;
+  size_t k = 0;
+  for (uint64_t first = 0; first < n && rc == ZKWG_RC_OK; first += p->E, ++k) {
+    ZkProveCtx& s = p->ctx[k % p->ctx.size()];
+    rc = prover_finish(p, s, blinding, out_proofs, status);
+    if (rc == ZKWG_RC_OK) rc = prover_enqueue(p, s, wit, stride, on_device ? wit : nullptr, nullptr, first, std::min<uint64_t>(p->E, n - first));
+  }
+  for (size_t j = 0; j < p->ctx.size(); ++j) {                    // drain, oldest first
+    const int r2 = prover_finish(p, p->ctx[(k + j) % p->ctx.size()], blinding, out_proofs, status);
+    if (rc == ZKWG_RC_OK) rc = r2;
+  }
+  if (rc != ZKWG_RC_OK) { hipDeviceSynchronize(); for (ZkProveCtx& s : p->ctx) s.busy = false; (void)hipGetLastError(); }
+  return rc;
+}
+int zkwg_prover_prove_witnesses(zkwg_prover_t* p, const uint8_t* witnesses, uint64_t stride, uint64_t n, const uint8_t* blinding, int32_t* status, uint8_t* out_proofs) {
+  return prove_witnesses(p, witnesses, stride, n, false, blinding, status, out_proofs);
+}
+int zkwg_prover_prove_witnesses_device(zkwg_prover_t* p, const void* d_witnesses, uint64_t stride, uint64_t n, const uint8_t* blinding, int32_t* status,
+                                       uint8_t* out_proofs) {
+  return prove_witnesses(p, d_witnesses, stride, n, true, blinding, status, out_proofs);
+}
 void zkwg_prover_destroy(zkwg_prover_t* p) { prover_free(p); }
 uint32_t zkwg_prover_emails_per_series(const zkwg_prover_t* p) { return p ? p->E : 0; }
 uint32_t zkwg_prover_contexts(const zkwg_prover_t* p) { return p ? (uint32_t)p->ctx.size() : 0; }
 
 int zkwg_prover_prove_prepared(zkwg_prover_t* p, const void* d_in, uint64_t n, const void* d_scratch, const uint64_t* indices, uint64_t n_idx,
                                const uint8_t* blinding, uint8_t* out_proofs) {
-  if (!p || !d_in || !d_scratch || !indices || !blinding || !out_proofs) return ZKWG_RC_BAD_ARG;
+  if (!p || !p->c || !d_in || !d_scratch || !indices || !blinding || !out_proofs) return ZKWG_RC_BAD_ARG;
   if (hipSetDevice(p->device) != hipSuccess) return ZKWG_RC_HIP_ERROR;
   for (uint64_t i = 0; i < n_idx; ++i) if (indices[i] >= n) return ZKWG_RC_BAD_ARG;
   int rc = ZKWG_RC_OK;
@@ -353,7 +425,7 @@ int zkwg_prover_prove_prepared(zkwg_prover_t* p, const void* d_in, uint64_t n, c
 // inputs -> proofs: n packed input records (zkwg_pack_input) on the host -> status[n] (circom_runtime codes) and, for every email whose
 // witness exists (status 0), its proof; the proof bytes of a failed email are zero
 int zkwg_prover_prove_batch(zkwg_prover_t* p, const uint8_t* packed, uint64_t n, const uint8_t* blinding, int32_t* status, uint8_t* out_proofs) {
-  if (!p || !packed || !blinding || !status || !out_proofs) return ZKWG_RC_BAD_ARG;
+  if (!p || !p->c || !packed || !blinding || !status || !out_proofs) return ZKWG_RC_BAD_ARG;
   if (n == 0) return ZKWG_RC_OK;
   if (hipSetDevice(p->device) != hipSuccess) return ZKWG_RC_HIP_ERROR;
   zkwg_circuit_t* c = p->c;

@@ -6,6 +6,10 @@
 //     node prove.js <circuit> <input.json> <circuit.zkey> <proofs.json> [device]
 //     node prove.js <circuit> <input.json> <circuit.zkey> <circuit.r1cs> <nRows> <proofs.json> [device]
 //
+//     node prove.js --wtns <witness.wtns> <circuit.zkey> <proof.json> <public.json> [device]
+//
+// Third form: `snarkjs groth16 prove` -- zkwg.groth16.prove(zkey, wtns) for the key of any BN254 groth16 circuit and the .wtns its own
+// witness calculator wrote; no circuit description at all.
 // <circuit> as for generate_witness.js (EmailVerifier(1024,1536,121,17,0,0,0,0) or a JSON of zkwg.Circuit options).  First form: the
 // zkey alone, as `fullProve(input, wasm, zkey)` takes it -- its section 4 is the constraint system.  Second form: the system from
 // <circuit.r1cs> over the circuit's witness layout with the nPublic + 1 rows snarkjs appends to A (python -m zkwg.r1cs --public-rows 1
@@ -16,6 +20,13 @@ const z = require('./zkwg.js');
 
 async function main() {
   const a = process.argv.slice(2);
+  if (a[0] === '--wtns') {
+    if (a.length < 5) { console.error('Usage: node prove.js --wtns <witness.wtns> <circuit.zkey> <proof.json> <public.json> [device]'); process.exit(2); }
+    const r = await z.groth16.prove(a[2], a[1], { device: a[5] === undefined ? 0 : Number(a[5]) });
+    fs.writeFileSync(a[3], JSON.stringify(r.proof, null, 1));
+    fs.writeFileSync(a[4], JSON.stringify(r.publicSignals, null, 1));
+    process.exit(0);
+  }
   if (a.length < 4) { console.error('Usage: node prove.js <circuit> <input.json> <circuit.zkey> [<circuit.r1cs> <nRows>] <proofs.json> [device]'); process.exit(2); }
   const withR1cs = a.length >= 6;
   const outPath = withR1cs ? a[5] : a[3], devArg = withR1cs ? a[6] : a[4];

@@ -334,6 +334,50 @@ const wtns = {
   },
 };
 
+/** snarkjs-shaped `groth16.prove(zkey, wtns)` / `groth16.fullProve(input, circuit, zkey)` on the device, for the key of ANY BN254
+ * groth16 circuit (include/zkwg.h zkwg_prover_create_wtns / zkwg_prover_prove_witnesses; reference call site
+ * packages/helpers/src/chunked-zkey.ts:80-84).  `zkey` / `wtns`: a path, a Buffer / Uint8Array, or {type: "mem", data} as in snarkjs.
+ * The device prover of a key is built once and kept (keyed by the path, or by the bytes' SHA-256): a second call proves at once. */
+const memOrFile = (x) => (typeof x === 'string' ? fs.readFileSync(x) : Buffer.from(x && x.type === 'mem' ? x.data : x));
+const groth16 = {
+  _cache: new Map(),
+  _prover(zkey, device) {
+    const dev = device === undefined ? 0 : device;
+    const key = dev + ':' + (typeof zkey === 'string' ? 'path:' + require('path').resolve(zkey)
+      : 'sha256:' + require('crypto').createHash('sha256').update(memOrFile(zkey)).digest('hex'));
+    let p = groth16._cache.get(key);
+    if (!p) { p = addon.createProverWtns(dev, memOrFile(zkey), 1); groth16._cache.set(key, p); }
+    return p;
+  },
+  /** -> Promise<{proof, publicSignals}>; opts: {device, blinding: [r, s] bigints (default: random)} */
+  async prove(zkey, wtnsFile, opts) {
+    opts = opts || {};
+    const p = groth16._prover(zkey, opts.device);
+    const file = memOrFile(wtnsFile);
+    const { nWitness, offset } = addon.wtnsParse(file);
+    if (nWitness !== p.nVars) throw new Error('Invalid witness length. Circuit: ' + p.nVars + ', witness: ' + nWitness);
+    const values = Buffer.from(file.subarray(offset, offset + 32 * nWitness));
+    const bl = Buffer.alloc(64);
+    const rs = opts.blinding || [Prover.randomFr(), Prover.randomFr()];
+    rs.forEach((v, i) => { let x = BigInt(v) % FIELD_MODULUS; for (let k = 0; k < 32; ++k) { bl[32 * i + k] = Number(x & 255n); x >>= 8n; } });
+    const r = await addon.proveWitnesses(p.handle, values, bl);
+    if (r.status[0] !== 0) throw new Error(addon.strerror(r.status[0]));
+    const num = (buf, o) => { let x = 0n; for (let k = 31; k >= 0; --k) x = (x << 8n) | BigInt(buf[o + k]); return x.toString(); };
+    const q = r.proofs;
+    const proof = { pi_a: [num(q, 0), num(q, 32), "1"], pi_b: [[num(q, 64), num(q, 96)], [num(q, 128), num(q, 160)], ["1", "0"]],
+      pi_c: [num(q, 192), num(q, 224), "1"], protocol: "groth16", curve: "bn128" };
+    const publicSignals = [];
+    for (let i = 1; i <= p.nPublic; ++i) publicSignals.push(num(values, 32 * i));
+    return { proof, publicSignals };
+  },
+  /** wtns.calculate + prove; `circuit`: a zkwg Circuit (where the reference passes the path of the circom WASM) */
+  async fullProve(input, circuit, zkey, opts) {
+    const w = { type: 'mem' };
+    await wtns.calculate(input, circuit, w);
+    return groth16.prove(zkey, w, opts);
+  },
+};
+
 /** The compiled circuit's `.r1cs`, for circom_tester-style `checkConstraints(witness)` on the device
  * (packages/circuits/tests/email-verifier.test.ts:44). */
 class R1cs {
@@ -363,4 +407,4 @@ function symbols(circuit) {
   return names;
 }
 
-module.exports = { symbols, R1cs, Circuit, WitnessCalculator, MultiCalculator, Prover, Tester, tester, wtns, FIELD_MODULUS, MAIN_EMAIL_VERIFIER, MAIN_SHA256_BYTES, MAIN_RSA_VERIFIER, MAIN_FP_MUL };
+module.exports = { symbols, R1cs, Circuit, WitnessCalculator, MultiCalculator, Prover, Tester, tester, wtns, groth16, FIELD_MODULUS, MAIN_EMAIL_VERIFIER, MAIN_SHA256_BYTES, MAIN_RSA_VERIFIER, MAIN_FP_MUL };

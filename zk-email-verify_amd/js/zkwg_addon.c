@@ -470,12 +470,14 @@ static napi_value CreateProverZkey(napi_env env, napi_callback_info info) {
 }
 typedef struct {
   zkwg_prover_t* p; const uint8_t* in; const uint8_t* blinding; uint64_t n;
+  uint64_t wit_stride;                 /* != 0: `in` holds n witnesses (zkwg_prover_prove_witnesses) */
   int32_t* status; uint8_t* proofs; int rc;
   napi_deferred deferred; napi_async_work work; napi_ref in_ref, bl_ref;
 } prove_job;
 static void prove_execute(napi_env env, void* data) {
   prove_job* j = (prove_job*)data; (void)env;
-  j->rc = zkwg_prover_prove_batch(j->p, j->in, j->n, j->blinding, j->status, j->proofs);
+  j->rc = j->wit_stride ? zkwg_prover_prove_witnesses(j->p, j->in, j->wit_stride, j->n, j->blinding, j->status, j->proofs)
+                        : zkwg_prover_prove_batch(j->p, j->in, j->n, j->blinding, j->status, j->proofs);
 }
 static void prove_complete(napi_env env, napi_status st, void* data) {
   prove_job* j = (prove_job*)data; (void)st;
@@ -524,6 +526,69 @@ static napi_value ProveBatch(napi_env env, napi_callback_info info) {
   return promise;
 }
 
+/* ---- groth16.prove(zkey, wtns) for any key: the prover of witnesses (zkwg_prover_create_wtns; no circuit handle) ------------------ */
+/* createProverWtns(device, zkey: Buffer, slots) -> {handle, nVars, nPublic} */
+static napi_value CreateProverWtns(napi_env env, napi_callback_info info) {
+  size_t argc = 3; napi_value argv[3];
+  NAPI_OK(napi_get_cb_info(env, info, &argc, argv, NULL, NULL));
+  int32_t device = 0; uint32_t slots = 1;
+  napi_get_value_int32(env, argv[0], &device);
+  void* zkey; size_t zkey_len;
+  NAPI_OK(napi_get_buffer_info(env, argv[1], &zkey, &zkey_len));
+  if (argc > 2) napi_get_value_uint32(env, argv[2], &slots);
+  zkwg_prover_t* pv = NULL;
+  int rc = zkwg_prover_create_wtns(device, (const uint8_t*)zkey, zkey_len, slots, &pv);
+  if (rc != ZKWG_RC_OK) { napi_throw_error(env, NULL, zkwg_strerror(rc)); return NULL; }
+  napi_value obj, ext, v;
+  NAPI_OK(napi_create_object(env, &obj));
+  NAPI_OK(napi_create_external(env, pv, prover_finalize, NULL, &ext));
+  NAPI_OK(napi_set_named_property(env, obj, "handle", ext));
+  NAPI_OK(napi_create_double(env, (double)zkwg_prover_witness_len(pv), &v));
+  NAPI_OK(napi_set_named_property(env, obj, "nVars", v));
+  NAPI_OK(napi_create_uint32(env, zkwg_prover_num_public(pv), &v));
+  NAPI_OK(napi_set_named_property(env, obj, "nPublic", v));
+  return obj;
+}
+/* wtnsParse(file: Buffer) -> {nWitness, offset} (zkwg_wtns_parse); throws for anything that is not a BN254 .wtns */
+static napi_value WtnsParse(napi_env env, napi_callback_info info) {
+  size_t argc = 1; napi_value argv[1];
+  NAPI_OK(napi_get_cb_info(env, info, &argc, argv, NULL, NULL));
+  void* data; size_t len;
+  NAPI_OK(napi_get_buffer_info(env, argv[0], &data, &len));
+  uint64_t nw = 0, off = 0;
+  if (zkwg_wtns_parse((const uint8_t*)data, len, &nw, &off) != ZKWG_RC_OK) { napi_throw_error(env, NULL, "zkwg: not a BN254 .wtns file"); return NULL; }
+  napi_value obj, v;
+  NAPI_OK(napi_create_object(env, &obj));
+  NAPI_OK(napi_create_double(env, (double)nw, &v));
+  NAPI_OK(napi_set_named_property(env, obj, "nWitness", v));
+  NAPI_OK(napi_create_double(env, (double)off, &v));
+  NAPI_OK(napi_set_named_property(env, obj, "offset", v));
+  return obj;
+}
+/* proveWitnesses(prover, witnesses: Buffer (n x 32 nVars bytes), blinding: Buffer (64 bytes per witness)) -> Promise<{status, proofs}> */
+static napi_value ProveWitnesses(napi_env env, napi_callback_info info) {
+  size_t argc = 3; napi_value argv[3];
+  NAPI_OK(napi_get_cb_info(env, info, &argc, argv, NULL, NULL));
+  void* pv = NULL;
+  if (napi_get_value_external(env, argv[0], &pv) != napi_ok || !pv) { napi_throw_type_error(env, NULL, "zkwg: prover handle expected"); return NULL; }
+  void *data, *bl; size_t len, bl_len;
+  NAPI_OK(napi_get_buffer_info(env, argv[1], &data, &len));
+  NAPI_OK(napi_get_buffer_info(env, argv[2], &bl, &bl_len));
+  const uint64_t stride = 32 * zkwg_prover_witness_len((zkwg_prover_t*)pv);
+  if (len == 0 || stride == 0 || len % stride || bl_len != (len / stride) * 64) { napi_throw_range_error(env, NULL, "zkwg: witness / blinding buffers do not match the key"); return NULL; }
+  prove_job* j = (prove_job*)calloc(1, sizeof(prove_job));
+  j->p = (zkwg_prover_t*)pv; j->in = (const uint8_t*)data; j->blinding = (const uint8_t*)bl; j->n = len / stride; j->wit_stride = stride;
+  j->status = (int32_t*)calloc(j->n, 4); j->proofs = (uint8_t*)calloc(j->n, 256);
+  napi_value promise, name;
+  NAPI_OK(napi_create_promise(env, &j->deferred, &promise));
+  NAPI_OK(napi_create_reference(env, argv[1], 1, &j->in_ref));
+  NAPI_OK(napi_create_reference(env, argv[2], 1, &j->bl_ref));
+  NAPI_OK(napi_create_string_utf8(env, "zkwg.proveWitnesses", NAPI_AUTO_LENGTH, &name));
+  NAPI_OK(napi_create_async_work(env, NULL, name, prove_execute, prove_complete, j, &j->work));
+  NAPI_OK(napi_queue_async_work(env, j->work));
+  return promise;
+}
+
 /* symText(circuit) -> the layout's symbol table in `.sym` line format (zkwg_write_sym) */
 static napi_value SymText(napi_env env, napi_callback_info info) {
   size_t argc = 1; napi_value argv[1];
@@ -559,6 +624,9 @@ static napi_value Init(napi_env env, napi_value exports) {
       {"createProver", NULL, CreateProver, NULL, NULL, NULL, napi_default, NULL},
       {"createProverZkey", NULL, CreateProverZkey, NULL, NULL, NULL, napi_default, NULL},
       {"proveBatch", NULL, ProveBatch, NULL, NULL, NULL, napi_default, NULL},
+      {"createProverWtns", NULL, CreateProverWtns, NULL, NULL, NULL, napi_default, NULL},
+      {"wtnsParse", NULL, WtnsParse, NULL, NULL, NULL, napi_default, NULL},
+      {"proveWitnesses", NULL, ProveWitnesses, NULL, NULL, NULL, napi_default, NULL},
   };
   napi_define_properties(env, exports, sizeof(d) / sizeof(d[0]), d);
   return exports;

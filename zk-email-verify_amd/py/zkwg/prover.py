@@ -269,6 +269,77 @@ class Prover:
                 "pi_c": [str(p["pi_c"][0]), str(p["pi_c"][1]), "1"], "protocol": "groth16", "curve": "bn128"}
 
 
+STATUS_WITNESS_NOT_REDUCED = 7          # include/zkwg.h ZKWG_ERR_WITNESS_NOT_REDUCED
+
+
+class WitnessProver:
+    """`groth16.prove(zkey, wtns)` for any BN254 groth16 key: made from the .zkey alone (include/zkwg.h zkwg_prover_create_wtns; rows of A
+    and B from section 4, C.w = A.w o B.w, bases from sections 5-9), proves witnesses -- the values a `.wtns` file holds -- `slots` at a
+    time through the rolling contexts of the batched prover."""
+
+    def __init__(self, zkey_bytes, device=0, slots=8):
+        self.lib = _lib.load()
+        self.device = device
+        self._zkey = bytes(zkey_bytes)
+        h = C.c_void_p()
+        _check(self.lib.zkwg_prover_create_wtns(device, self._zkey, len(self._zkey), slots, C.byref(h)))
+        self._h = h
+        self.n_vars = self.lib.zkwg_prover_witness_len(h)
+        self.n_public = self.lib.zkwg_prover_num_public(h)
+        self.n_rows = self.lib.zkwg_prover_rows(h)
+
+    def __del__(self):
+        if getattr(self, "_h", None):
+            self.lib.zkwg_prover_destroy(self._h)
+            self._h = None
+
+    def _values(self, w):
+        from .wtns import read_wtns
+        w = bytes(w)
+        if w[:4] == b"wtns":
+            return read_wtns(w, n_vars=self.n_vars)[1]
+        if len(w) != 32 * self.n_vars:
+            raise ZkwgError(f"a witness of {len(w)} bytes, the key has {self.n_vars} wires")
+        return w
+
+    def prove_bytes(self, witnesses, blinding):
+        """witnesses: bytes of k witnesses back to back (32 * nVars each), a list of `.wtns` blobs / value blobs, or a torch uint8 device
+        tensor of k * 32 * nVars bytes; blinding = [(r, s)] per witness -> (status list, 256 bytes per proof; zeros where status != 0)"""
+        stride = 32 * self.n_vars
+        bl = b"".join(int(r % R).to_bytes(32, "little") + int(s % R).to_bytes(32, "little") for r, s in blinding)
+        n = len(blinding)
+        st = (C.c_int32 * n)()
+        out = (C.c_uint8 * (256 * n))()
+        if hasattr(witnesses, "data_ptr"):
+            if witnesses.numel() * witnesses.element_size() != n * stride:
+                raise ZkwgError("the tensor does not hold one witness per blinding pair")
+            _check(self.lib.zkwg_prover_prove_witnesses_device(self._h, witnesses.data_ptr(), stride, n, bl, st, out))
+        else:
+            raw = b"".join(self._values(w) for w in witnesses) if isinstance(witnesses, (list, tuple)) else bytes(witnesses)
+            if len(raw) != n * stride:
+                raise ZkwgError("not one witness per blinding pair")
+            _check(self.lib.zkwg_prover_prove_witnesses(self._h, raw, stride, n, bl, st, out))
+        return list(st), bytes(out)
+
+    def prove(self, witnesses, blinding):
+        """-> (status list, proofs in the form Prover.proof_json takes; None where status != 0)"""
+        st, raw = self.prove_bytes(witnesses, blinding)
+        proofs = Prover._proofs_from_bytes(raw, len(st))
+        return st, [p if st[i] == 0 else None for i, p in enumerate(proofs)]
+
+    def public_signals(self, witness):
+        """publicSignals of snarkjs: the wires 1 .. nPublic as decimal strings"""
+        v = self._values(witness)
+        return [str(int.from_bytes(v[32 * i:32 * i + 32], "little")) for i in range(1, self.n_public + 1)]
+
+    def abc_device(self, d_witnesses, n, stream=None):
+        """zk_zkey_abc alone: n device-resident witnesses -> tensor of n records A.w | B.w | C.w (Montgomery form)"""
+        import torch
+        d_abc = torch.empty(n * 96 * self.n_rows, dtype=torch.uint8, device=d_witnesses.device)
+        _check(self.lib.zkwg_prover_abc_device(self._h, d_witnesses.data_ptr(), 32 * self.n_vars, n, d_abc.data_ptr(), 96 * self.n_rows, _stream_ptr(stream)))
+        return d_abc
+
+
 def point_from_montgomery(raw):
     """a sum as zkwg_msm_* returns it (affine, Montgomery form) -> standard-form integers: (x, y), ((x0, x1), (y0, y1)) or None"""
     if raw == bytes(len(raw)):
