@@ -598,6 +598,43 @@ int zkwg_expand_abc_host(const zkwg_circuit_t* c, const uint8_t* packed_inputs, 
 int zkwg_expand_full_host(const zkwg_circuit_t* c, const uint8_t* packed_inputs, uint64_t n_emails, uint8_t* scratch_host,
                           uint64_t first, uint64_t count, uint8_t* out, uint64_t out_stride);
 
+/* ---- the groth16 set-up: zKey.newZKey(r1cs, ptau) on the device (csrc/zkwg_setup_core.h) ----------------
+ * The step between "compute the witness" and "prove" of the reference's workflow (docs/zk-email-docs/UsageGuide/README.md:145-180,
+ * `snarkjs groth16 setup circuit.r1cs pot.ptau circuit.zkey`): a compiler-format .r1cs and a PREPARED powers-of-tau file give the
+ * initial key (gamma = delta = 1, no contributions) as a .zkey that zkwg_prover_create_zkey / zkwg_prover_create_wtns and snarkjs'
+ * provers read.  Section 10 is 64 zero bytes and a count of 0 (the circuit hash is not computed: `snarkjs zkey verify` refuses the
+ * file, no prover looks there).  Phase-2 contributions, preparing an unprepared file, chunked keys and other curves are not built.
+ *
+ * zkwg_setup_slices: the points the set-up reads, in the zkey's form (affine, little-endian Montgomery words, zeros = infinity), for
+ * the circuit's domain 2^power: [L_j(tau)]_1, [L_j(tau)]_2, [alpha L_j(tau)]_1, [beta L_j(tau)]_1 (2^power points each) and
+ * [L_j(tau)]_1 of the domain 2^(power + 1).  Host pointers (on_device = 0) or device pointers (1).  zkwg_ptau_parse fills it with
+ * pointers INTO the caller's buffer (an mmap: a power-21 file is 2 - 3 GB and is never copied); a caller may fill it by hand.
+ * zkwg_ptau_parse checks the prime, the power and every section size before it reads a point.  A file without the Lagrange sections
+ * 12 - 15 is refused ("Powers of tau is not prepared"), so is one whose power is below `power`.
+ *
+ * zkwg_zkey_new_size: the domain power the .r1cs needs (smallest p >= 1 with 2^p >= constraints + nPublic + 1) and the bytes of
+ * its key.  zkwg_zkey_new writes the key to out_zkey (host memory, cap >= that size).  It is a one-shot call: it allocates its device
+ * buffers, synchronises and frees them before it returns.  Refusals (ZKWG_RC_BAD_CONFIG, zkwg_last_error says which): whatever the
+ * .r1cs reader refuses, nPublic + 1 >= nVars, slices of another power, a slice point that is not on its curve or not reduced (checked
+ * on the device over every uploaded point), a wire with more than 2^27 terms in one sum. */
+typedef struct zkwg_setup_slices {
+  uint32_t power;
+  uint32_t on_device;
+  const void* tau_g1;         /* 2^power x 64 bytes */
+  const void* tau_g2;         /* 2^power x 128 bytes */
+  const void* alpha_tau_g1;   /* 2^power x 64 bytes */
+  const void* beta_tau_g1;    /* 2^power x 64 bytes */
+  const void* tau_g1_next;    /* 2^(power + 1) x 64 bytes */
+  uint8_t alpha1[64], beta1[64], beta2[128];      /* the key's header points (always host memory) */
+} zkwg_setup_slices;
+int zkwg_ptau_parse(const uint8_t* ptau, uint64_t len, uint32_t power, zkwg_setup_slices* out);
+int zkwg_zkey_new_size(const uint8_t* r1cs, uint64_t len, uint32_t* power, uint64_t* zkey_bytes);
+int zkwg_zkey_new(int device, const uint8_t* r1cs, uint64_t len, const zkwg_setup_slices* slices, uint8_t* out_zkey, uint64_t cap,
+                  uint64_t* out_len);
+/* seconds and group operations of the last zkwg_zkey_new of this thread (tools/bench_setup.py):
+ * {parse + plans, upload + curve check, sum A, sum B1, sum B2, sum K, H copy + download}, then per sum {additions, doublings} */
+void zkwg_zkey_new_stats(double seconds[7], uint64_t ops[8]);
+
 /* ---- the compact image as a device-side interchange format --------------------------
  * zkwg_prepare_device leaves, per email, a compact IMAGE in the scratch buffer (~0.45 MB instead of the 57 MB
  * witness of EmailVerifier(1024,1536)): `bits` (u64 words of LSB-first bit groups), `small` (u32 values) and

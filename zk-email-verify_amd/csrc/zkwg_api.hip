@@ -256,6 +256,7 @@ const char* zkwg_strerror(int rc) {
 
 static thread_local std::string g_last_error;
 const char* zkwg_last_error(void) { return g_last_error.c_str(); }
+void zk_set_last_error(const char* m) { g_last_error = m; }      // for the C-ABI files beside this one (zkwg_setup_api.hip)
 
 static int create_impl(const zkwg_config* cfg_in, int device, const char* sym_text, uint64_t sym_len,
                        const char* alias_text, uint64_t alias_len, zkwg_circuit_t** out,

@@ -1,8 +1,9 @@
 """snarkjs `.zkey` (groth16) reader / writer: the file `groth16.prove(zkey, wtns)` takes its bases from (reference call site:
 packages/helpers/src/chunked-zkey.ts:80-84; the reference's helpers download it in chunks `circuit.zkeyb ... zkeyk`, :9-77).
 
-No .zkey exists offline, so the layout below is restated from snarkjs' published code (src/zkey_utils.js,
-src/zkey_new.js) [EXT] and is UNPINNED until a real file is read: the round trip write -> read is what the tests check.
+No .zkey made by snarkjs exists offline -- the keys of this tree are made by zkwg.setup (zkwg_zkey_new) or from a known
+trapdoor by the tests -- so the layout below is restated from snarkjs' published code (src/zkey_utils.js, src/zkey_new.js) [EXT] and is
+UNPINNED until a real file is read: the round trip write -> read is what the tests check.
 
     "zkey" | u32 version = 1 | u32 nSections = 10 | sections: u32 id, u64 size, payload
     1  u32 protocol (1 = groth16)
@@ -21,9 +22,10 @@ R = 2188824287183927522224640574525727508854836440041603434369820418657580849561
 Q = 21888242871839275222246405745257275088696311157297823662689037894645226208583
 
 
-def read_zkey(data):
+def read_zkey(data, coeffs=True):
     """-> dict: n_vars, n_public, domain_size, power, points alpha1 ... delta2 (bytes as stored), ic / a / b1 / b2 / c / h (bytes of the
-    whole section), coeffs = [(matrix, constraint, signal, coefficient)] (standard-form integers)"""
+    whole section), coeffs = [(matrix, constraint, signal, coefficient)] (standard-form integers; [] with coeffs=False: section 4 of a
+    large key is tens of millions of Python tuples)"""
     if data[:4] != b"zkey":
         raise ValueError("not a .zkey file")
     version, nsec = struct.unpack_from("<II", data, 4)
@@ -67,7 +69,7 @@ def read_zkey(data):
             raise ValueError(f".zkey: section {sid} holds {size} bytes, expected {want[sid]}")
         out[name] = bytes(data[o:o + size])
     out["coeffs"] = []
-    if 4 in sec:
+    if 4 in sec and coeffs:
         o, _ = sec[4]
         n = struct.unpack_from("<I", data, o)[0]
         o += 4
@@ -96,6 +98,29 @@ def write_zkey(n_vars, n_public, domain_size, points, ic, a, b1, b2, c, h, coeff
         out.append(struct.pack("<IQ", sid, len(payload)))
         out.append(payload)
     return b"".join(out)
+
+
+def _std(b):
+    return int.from_bytes(b, "little") * pow(1 << 256, -1, Q) % Q
+
+
+def _g1_json(b):
+    return ["0", "1", "0"] if not any(b) else [str(_std(b[:32])), str(_std(b[32:64])), "1"]
+
+
+def _g2_json(b):
+    if not any(b):
+        return [["0", "0"], ["1", "0"], ["0", "0"]]
+    return [[str(_std(b[:32])), str(_std(b[32:64]))], [str(_std(b[64:96])), str(_std(b[96:128]))], ["1", "0"]]
+
+
+def verification_key(data):
+    """the snarkjs verification_key.json of a .zkey (`snarkjs zkey export verificationkey`): vk_alpha_1, vk_beta_2, vk_gamma_2, vk_delta_2
+    from the header and IC from section 3, standard-form decimal strings (vk_alphabeta_12, which no verifier needs, is not computed)"""
+    z = read_zkey(data, coeffs=False) if not isinstance(data, dict) else data
+    return {"protocol": "groth16", "curve": "bn128", "nPublic": z["n_public"],
+            "vk_alpha_1": _g1_json(z["alpha1"]), "vk_beta_2": _g2_json(z["beta2"]), "vk_gamma_2": _g2_json(z["gamma2"]),
+            "vk_delta_2": _g2_json(z["delta2"]), "IC": [_g1_json(z["ic"][64 * i:64 * i + 64]) for i in range(z["n_public"] + 1)]}
 
 
 def proving_key_from_zkey(device, data):
