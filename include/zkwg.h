@@ -603,7 +603,7 @@ int zkwg_expand_full_host(const zkwg_circuit_t* c, const uint8_t* packed_inputs,
  * `snarkjs groth16 setup circuit.r1cs pot.ptau circuit.zkey`): a compiler-format .r1cs and a PREPARED powers-of-tau file give the
  * initial key (gamma = delta = 1, no contributions) as a .zkey that zkwg_prover_create_zkey / zkwg_prover_create_wtns and snarkjs'
  * provers read.  Section 10 is 64 zero bytes and a count of 0 (the circuit hash is not computed: `snarkjs zkey verify` refuses the
- * file, no prover looks there).  Phase-2 contributions, preparing an unprepared file, chunked keys and other curves are not built.
+ * file, no prover looks there).  Preparing an unprepared file, chunked keys and other curves are not built; phase 2: below.
  *
  * zkwg_setup_slices: the points the set-up reads, in the zkey's form (affine, little-endian Montgomery words, zeros = infinity), for
  * the circuit's domain 2^power: [L_j(tau)]_1, [L_j(tau)]_2, [alpha L_j(tau)]_1, [beta L_j(tau)]_1 (2^power points each) and
@@ -634,6 +634,35 @@ int zkwg_zkey_new(int device, const uint8_t* r1cs, uint64_t len, const zkwg_setu
 /* seconds and group operations of the last zkwg_zkey_new of this thread (tools/bench_setup.py):
  * {parse + plans, upload + curve check, sum A, sum B1, sum B2, sum K, H copy + download}, then per sum {additions, doublings} */
 void zkwg_zkey_new_stats(double seconds[7], uint64_t ops[8]);
+
+/* ---- phase 2: a contribution to a .zkey on the device (csrc/zkwg_phase2_core.h) -----------------------------
+ * The reference's workflow requires "Phase 2" after the powers of tau (docs/zk-email-docs/UsageGuide/README.md:149,178-180; its next
+ * command reads circuit_0001.zkey, the key AFTER a contribution): `snarkjs zkey contribute` / `zkey beacon`.  A contribution with
+ * secret k sets delta1' = k delta1, delta2' = k delta2, C_i' = k^-1 C_i (section 8), H_j' = k^-1 H_j (section 9); sections 1, 3 - 7 and
+ * alpha, beta, gamma are copied.  The record of section 10 (who contributed, the proof of knowledge of k) is the host layer's:
+ * zkwg/phase2.py.  Not built: `zkey verify`, the circuit hash, chunked keys.
+ *
+ * zkwg_point_scale_device: d_out[i] = scalar * d_points[i] for n affine points in the zkey's form (64 / 128 bytes, little-endian
+ * Montgomery words, zeros = infinity and stay zeros; group 1 / 2; device pointers, 16-byte aligned; d_out may be d_points).  scalar:
+ * 32 bytes, little-endian, standard form, ANY value below 2^256 (not reduced modulo the group order: a G2 point outside the subgroup
+ * is multiplied by the integer).  Every point is checked on its curve first; one that fails refuses the whole call: ZKWG_RC_BAD_CONFIG,
+ * zkwg_last_error says "curve".  The call allocates 280 (G1) / 488 (G2) bytes per point for at most 2^20 points at a time, works on
+ * hip_stream, synchronises it and frees its buffers before it returns.
+ *
+ * zkwg_zkey_apply_delta: the whole file operation, host memory in and out.  k: 32 bytes, little-endian, reduced modulo r by the call;
+ * k = 0 mod r is refused, so are a file zkwg_zkey_check's header reader refuses (truncated, section sizes against the header), a
+ * missing section 3, and a point of section 8, section 9 or delta that is not on its curve (ZKWG_RC_BAD_CONFIG + zkwg_last_error; the
+ * bytes of `out` are unspecified then).  section10: the payload the new file gets as its section 10, verbatim.  out: cap >= what
+ * zkwg_zkey_apply_delta_size gives for the same section10_len; the sections are written in the order 1 .. 10.  Sections 8 and 9 go
+ * through the device in pieces of 2^20 points (294 MB of device memory), so a key of any domain fits. */
+int zkwg_point_scale_device(int device, int group, const void* d_points, uint64_t n, const uint8_t* scalar, void* d_out, void* hip_stream);
+int zkwg_zkey_apply_delta_size(const uint8_t* zkey, uint64_t len, uint64_t section10_len, uint64_t* out_bytes);
+int zkwg_zkey_apply_delta(int device, const uint8_t* zkey, uint64_t len, const uint8_t* k, const uint8_t* section10, uint64_t section10_len,
+                          uint8_t* out, uint64_t cap, uint64_t* out_len);
+/* seconds and group operations of the last zkwg_zkey_apply_delta of this thread (tools/bench_phase2.py): {parse + copy of the unchanged
+ * sections, upload + curve check, scaling of section 8, scaling of section 9, conversion + download}; {mixed additions, doublings} of
+ * section 8, then of section 9 */
+void zkwg_zkey_apply_delta_stats(double seconds[5], uint64_t ops[4]);
 
 /* ---- the compact image as a device-side interchange format --------------------------
  * zkwg_prepare_device leaves, per email, a compact IMAGE in the scratch buffer (~0.45 MB instead of the 57 MB

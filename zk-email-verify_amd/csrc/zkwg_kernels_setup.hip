@@ -69,7 +69,7 @@ template <class C> __global__ __launch_bounds__(64) void zk_setup_affine_k(const
   constexpr u32 per = 64u / C::LANES;
   const u32 i = blockIdx.x * per + threadIdx.x / C::LANES, h = threadIdx.x % C::LANES;
   if (i >= n) return;
-  zk_setup_affine<C>(acc[(u64)i * C::LANES + h], den[i], out + seg_wire[i], h);
+  zk_setup_affine<C>(acc[(u64)i * C::LANES + h], den[i], out + (seg_wire ? seg_wire[i] : i), h);      // (no map: point i -> out[i])
 }
 // the curve check (and the tables' form) of n uploaded points; *bad is raised when a point fails
 template <class C> __global__ __launch_bounds__(64) void zk_setup_prepare(const typename C::Affine* in, typename C::Affine* out, u64 n, u32* bad) {
@@ -84,6 +84,17 @@ __global__ __launch_bounds__(256) void zk_setup_odd_copy(const uint4* in, uint4*
   if (t < 4 * n) out[t] = in[4 * (2 * (t >> 2) + 1) + (t & 3u)];
 }
 
+// n accumulators -> canonical affine points in the zkey's form: out[seg_wire[i]] (out[i] without a map); den, pref: n values of room each
+template <class C>
+static void zk_setup_to_affine_t(const void* acc, Fq29* den, Fq29* pref, const u32* seg_wire, void* out, u32 n, hipStream_t st) {
+  typedef Xyzz29<typename C::F> X;
+  constexpr u32 per = 64u / C::DEV_LANES;
+  if (!n) return;
+  const u32 n_lanes = (n + ZK_SETUP_INV_BATCH - 1) / ZK_SETUP_INV_BATCH;
+  hipLaunchKernelGGL(zk_setup_den_k<C>, dim3((n + per - 1) / per), dim3(64), 0, st, (const X*)acc, den, n);
+  hipLaunchKernelGGL(zk_setup_inv_k, dim3((n_lanes + 63) / 64), dim3(64), 0, st, den, pref, n, n_lanes);
+  hipLaunchKernelGGL(zk_setup_affine_k<C>, dim3((n + per - 1) / per), dim3(64), 0, st, (const X*)acc, (const Fq29*)den, seg_wire, (typename C::Affine*)out, n);
+}
 template <class C>
 static void zk_setup_run_t(const ZkSetupRun& r, hipStream_t st) {
   typedef Xyzz29<typename C::F> X;
@@ -92,15 +103,15 @@ static void zk_setup_run_t(const ZkSetupRun& r, hipStream_t st) {
   if (r.n_short) hipLaunchKernelGGL(zk_setup_short<C>, dim3((r.n_short + per - 1) / per), dim3(64), 0, st, ZkSetupArgs<C>{r.T, tab, r.shorts, r.n_short, (X*)r.acc, nullptr});
   if (r.n_chunk) hipLaunchKernelGGL(zk_setup_chunk<C>, dim3(r.n_chunk), dim3(64), 0, st, ZkSetupArgs<C>{r.T, tab, r.chunks, r.n_chunk, (X*)r.part, nullptr});
   if (r.n_join) hipLaunchKernelGGL(zk_setup_join_wave<C>, dim3(r.n_join), dim3(64), 0, st, ZkSetupArgs<C>{r.T, tab, r.joins, r.n_join, (X*)r.acc, (const X*)r.part});
-  if (!r.n_seg) return;
-  const u32 n_lanes = (r.n_seg + ZK_SETUP_INV_BATCH - 1) / ZK_SETUP_INV_BATCH;
-  hipLaunchKernelGGL(zk_setup_den_k<C>, dim3((r.n_seg + per - 1) / per), dim3(64), 0, st, (const X*)r.acc, r.den, r.n_seg);
-  hipLaunchKernelGGL(zk_setup_inv_k, dim3((n_lanes + 63) / 64), dim3(64), 0, st, r.den, r.pref, r.n_seg, n_lanes);
-  hipLaunchKernelGGL(zk_setup_affine_k<C>, dim3((r.n_seg + per - 1) / per), dim3(64), 0, st, (const X*)r.acc, (const Fq29*)r.den, r.seg_wire, (typename C::Affine*)r.out, r.n_seg);
+  zk_setup_to_affine_t<C>(r.acc, r.den, r.pref, r.seg_wire, r.out, r.n_seg, st);
 }
 void zk_setup_run_launch(int group, const ZkSetupRun& r, hipStream_t st) {
   if (group == 1) zk_setup_run_t<ZkEcG1>(r, st);
   else zk_setup_run_t<ZkEcG2>(r, st);
+}
+void zk_setup_to_affine_launch(int group, const void* acc, Fq29* den, Fq29* pref, const u32* seg_wire, void* out, u32 n, hipStream_t st) {
+  if (group == 1) zk_setup_to_affine_t<ZkEcG1>(acc, den, pref, seg_wire, out, n, st);
+  else zk_setup_to_affine_t<ZkEcG2>(acc, den, pref, seg_wire, out, n, st);
 }
 void zk_setup_prepare_launch(int group, const void* in, void* out, u64 n, u32* bad, hipStream_t st) {
   if (group == 1) hipLaunchKernelGGL(zk_setup_prepare<ZkEcG1>, dim3((u32)((n + 63) / 64)), dim3(64), 0, st, (const G1Affine*)in, (G1Affine*)out, n, bad);

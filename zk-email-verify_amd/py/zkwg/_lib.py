@@ -184,6 +184,10 @@ def load():
         "zkwg_zkey_new_size": (i32, [vp, u64, C.POINTER(u32), C.POINTER(u64)]),
         "zkwg_zkey_new": (i32, [i32, vp, u64, C.POINTER(SetupSlices), vp, u64, C.POINTER(u64)]),
         "zkwg_zkey_new_stats": (None, [C.POINTER(C.c_double), C.POINTER(u64)]),
+        "zkwg_point_scale_device": (i32, [i32, i32, vp, u64, vp, vp, vp]),
+        "zkwg_zkey_apply_delta_size": (i32, [vp, u64, u64, C.POINTER(u64)]),
+        "zkwg_zkey_apply_delta": (i32, [i32, vp, u64, vp, vp, u64, vp, u64, C.POINTER(u64)]),
+        "zkwg_zkey_apply_delta_stats": (None, [C.POINTER(C.c_double), C.POINTER(u64)]),
         "zkwg_groth16_assemble": (i32, [vp] * 15),
         "zkwg_calculate_batch_resident": (i32, [vp, vp, u64, vp, vp, u64, u64, vp, vp]),
         "zkwg_resident_placement": (i32, [vp, C.POINTER(C.c_float), i32, C.POINTER(C.c_int)]),
@@ -211,4 +215,5 @@ EXPORTS = [
     "zkwg_msm_g2_device", "zkwg_msm_create_g2", "zkwg_msm_create_device", "zkwg_msm_group", "zkwg_fixed_base_device", "zkwg_groth16_assemble", "zkwg_msm_enqueue_device", "zkwg_msm_finish_host", "zkwg_msm_create_ex", "zkwg_msm_work_bytes_batch", "zkwg_msm_lists_bytes", "zkwg_msm_estimate_work_bytes", "zkwg_msm_table_bytes", "zkwg_msm_precomputed", "zkwg_msm_enqueue_batch_device", "zkwg_msm_classify_device", "zkwg_msm_enqueue_lists_device", "zkwg_prover_emails_per_series", "zkwg_prover_contexts", "zkwg_prover_create_zkey", "zkwg_prover_create", "zkwg_prover_destroy", "zkwg_prover_prove_prepared", "zkwg_prover_prove_batch", "zkwg_prover_create_wtns", "zkwg_prover_witness_len", "zkwg_prover_num_public", "zkwg_prover_rows", "zkwg_prover_prove_witnesses",
     "zkwg_prover_prove_witnesses_device", "zkwg_prover_abc_device", "zkwg_wtns_parse", "zkwg_zkey_check", "zkwg_device_alloc_chunked", "zkwg_device_free_chunked", "zkwg_device_alloc_chunked_ex",
     "zkwg_ptau_parse", "zkwg_zkey_new_size", "zkwg_zkey_new", "zkwg_zkey_new_stats",
+    "zkwg_point_scale_device", "zkwg_zkey_apply_delta_size", "zkwg_zkey_apply_delta", "zkwg_zkey_apply_delta_stats",
 ]

@@ -1,0 +1,315 @@
+"""python -m zkwg.phase2 contribute in.zkey out.zkey --name N [--entropy E]
+python -m zkwg.phase2 beacon in.zkey out.zkey HASHHEX EXP --name N
+-- "Phase 2" of the reference's workflow on the device (docs/zk-email-docs/UsageGuide/README.md:149,178-180: `snarkjs zkey contribute` /
+`zkey beacon`; the guide's next command reads circuit_0001.zkey, the key AFTER a contribution, :206).  The key python -m zkwg.setup writes
+has delta = 1: anyone can forge proofs under it.  A contribution with secret k turns delta into k delta (delta1, delta2 times k, the C and
+H bases times 1 / k: zkwg_zkey_apply_delta, csrc/zkwg_phase2_core.h, csrc/zkwg_kernels_phase2.hip) and appends a record to section 10.
+
+THE SCALAR.  k = BLAKE2b-512(tag | seed) mod r, hashed again while it is 0.  contribute: seed = 64 bytes of os.urandom | entropy;
+beacon: seed = SHA-256 iterated 2^EXP times over the beacon hash (a sequential chain: host).  hashlib only.
+
+THE RECORD (section 10: 64-byte circuit hash, u32 count, records), as snarkjs writes it -- restated from its published
+src/zkey_utils.js [EXT], UNPINNED like the container itself (zkwg/zkey.py): RECORD_POINTS, then a 64-byte transcript, u32 length of the
+parameters, and the parameters as (tag byte, value) in the order of PARAMS.
+    deltaAfter  delta1 after this contribution            g1_s = s G, g1_sx = (s k) G for a random s
+    g2_spx = k g2_sp, g2_sp = challenge_g2(transcript)    transcript = BLAKE2b-512(circuit hash | earlier records | g1_s | g1_sx)
+Knowledge of k: e(g1_s, g2_spx) = e(g1_sx, g2_sp) and e(delta1 before, g2_spx) = e(deltaAfter, g2_sp).
+
+THE CHALLENGE POINT IS ZKWG'S OWN.  snarkjs derives g2_sp from a ChaCha stream seeded with the transcript, which cannot be restated
+offline; here it is try-and-increment: x in Fq2 from BLAKE2b(tag | transcript | counter | half), y = sqrt(x^3 + 3 / (9 + i)) in Python
+integers (q = 3 mod 4; Fq2 roots through the norm), then times the twist's cofactor 2 q - r on the device (zkwg_point_scale_device:
+the one scalar here above r).  Nobody knows its discrete logarithm -- a multiple of the generator would let the first contribution be
+forged.  `snarkjs zkey verify` therefore does NOT accept the record (nor the circuit hash, which stays as the file holds it: 64 zero
+bytes after zkwg.setup); every prover and verifier reads the key."""
+import argparse
+import ctypes as C
+import hashlib
+import mmap
+import os
+import struct
+import sys
+
+from . import _lib, zkey
+
+R, Q = zkey.R, zkey.Q
+COFACTOR_G2 = 2 * Q - R
+TAG_SCALAR, TAG_POK, TAG_G2 = b"zkwg phase2 scalar v1", b"zkwg phase2 pok v1", b"zkwg phase2 challenge v1"
+RECORD_POINTS = (("delta_after", 64), ("g1_s", 64), ("g1_sx", 64), ("g2_spx", 128))
+# (tag, field, kind): u8 = one byte; bytes / str = a length byte and that many bytes.  A field that is None / 0 / empty is not written.
+PARAMS = ((1, "type", "u8"), (2, "num_iterations_exp", "u8"), (3, "beacon_hash", "bytes"), (4, "name", "str"))
+TYPE_BEACON = 1
+
+
+class Phase2Error(ValueError):
+    pass
+
+
+def _fail(lib, rc):
+    msg = lib.zkwg_last_error().decode() if rc == -1 else ""
+    raise Phase2Error(f"{lib.zkwg_strerror(rc).decode()}{': ' + msg if msg else ''}")
+
+
+def derive_scalar(seed_bytes, tag=TAG_SCALAR):
+    """-> k in [1, r): BLAKE2b-512(tag | seed) mod r, hashed again while 0"""
+    h = hashlib.blake2b(tag + bytes(seed_bytes), digest_size=64).digest()
+    while int.from_bytes(h, "little") % R == 0:
+        h = hashlib.blake2b(tag + h, digest_size=64).digest()
+    return int.from_bytes(h, "little") % R
+
+
+def beacon_seed(beacon_hash, num_iterations_exp):
+    h = bytes(beacon_hash)
+    for _ in range(1 << num_iterations_exp):
+        h = hashlib.sha256(h).digest()
+    return h
+
+
+# ---- section 10 -------------------------------------------------------------------------------------------------------------------------------
+def _pack_params(rec):
+    out = b""
+    for tag, field, kind in PARAMS:
+        v = rec.get(field)
+        if not v:
+            continue
+        if kind == "u8":
+            out += bytes([tag, v])
+        else:
+            b = v.encode()[:64] if kind == "str" else bytes(v)
+            if len(b) > 255:
+                raise Phase2Error(f"{field} is longer than 255 bytes")
+            out += bytes([tag, len(b)]) + b
+    return out
+
+
+def pack_record(rec):
+    out = b"".join(rec[name] for name, _ in RECORD_POINTS)
+    assert len(out) == sum(size for _, size in RECORD_POINTS) and len(rec["transcript"]) == 64
+    params = _pack_params(rec)
+    return out + rec["transcript"] + struct.pack("<I", len(params)) + params
+
+
+def read_contributions(zkey_or_section10):
+    """a .zkey, or the payload of its section 10 -> (circuit hash, [record]); a record: the RECORD_POINTS (bytes as stored), transcript,
+    the PARAMS fields (None where absent) and raw, its bytes in the file.  A key without section 10: (64 zero bytes, [])"""
+    data = zkey_or_section10
+    if data[:4] == b"zkey":
+        sec = zkey.sections(data)
+        data = bytes(data[sec[10][0]:sec[10][0] + sec[10][1]]) if 10 in sec else b""
+    if len(data) == 0:
+        return bytes(64), []
+    if len(data) < 68:
+        raise Phase2Error("section 10 is shorter than its hash and count")
+    n = struct.unpack_from("<I", data, 64)[0]
+    pos, recs = 68, []
+    by_tag = {tag: (field, kind) for tag, field, kind in PARAMS}
+    fixed = sum(size for _, size in RECORD_POINTS) + 64 + 4
+    for _ in range(n):
+        if pos + fixed > len(data):
+            raise Phase2Error("section 10: a record runs past the end of the section")
+        rec, start = {field: None for _, field, _ in PARAMS}, pos
+        for name, size in RECORD_POINTS:
+            rec[name] = bytes(data[pos:pos + size])
+            pos += size
+        rec["transcript"] = bytes(data[pos:pos + 64])
+        plen = struct.unpack_from("<I", data, pos + 64)[0]
+        pos += 68
+        if pos + plen > len(data):
+            raise Phase2Error("section 10: the parameters of a record run past the end of the section")
+        p, end = pos, pos + plen
+        while p < end:
+            if data[p] not in by_tag or p + 2 > end:
+                raise Phase2Error("section 10: unknown or truncated parameter")
+            field, kind = by_tag[data[p]]
+            if kind == "u8":
+                rec[field] = data[p + 1]
+                p += 2
+            else:
+                ln = data[p + 1]
+                if p + 2 + ln > end:
+                    raise Phase2Error("section 10: truncated parameter")
+                v = bytes(data[p + 2:p + 2 + ln])
+                rec[field] = v.decode() if kind == "str" else v
+                p += 2 + ln
+        pos = end
+        rec["raw"] = bytes(data[start:pos])
+        recs.append(rec)
+    if pos != len(data):
+        raise Phase2Error("section 10: bytes after the last record")
+    return bytes(data[:64]), recs
+
+
+def pack_section10(circuit_hash, raw_records):
+    return bytes(circuit_hash) + struct.pack("<I", len(raw_records)) + b"".join(raw_records)
+
+
+# ---- the device ---------------------------------------------------------------------------------------------------------------------------------
+def scale_points(group, points, scalar, device=0):
+    """scalar * every point of `points` (bytes in the zkey's form; scalar: any integer below 2^256) -> bytes (zkwg_point_scale_device)"""
+    import torch
+    lib = _lib.load()
+    pt = 64 if group == 1 else 128
+    if len(points) % pt or not 0 <= scalar < 1 << 256:
+        raise Phase2Error("points must be whole and the scalar below 2^256")
+    if not points:
+        return b""
+    dev = torch.device("cuda", device)
+    d = torch.frombuffer(bytearray(points), dtype=torch.uint8).to(dev)
+    out = torch.empty_like(d)
+    rc = lib.zkwg_point_scale_device(device, group, d.data_ptr(), len(points) // pt, int(scalar).to_bytes(32, "little"), out.data_ptr(), 0)
+    if rc != 0:
+        _fail(lib, rc)
+    return bytes(out.cpu().numpy())
+
+
+def apply_delta(zkey_bytes, k, section10, device=0):
+    """the key with delta times k and `section10` as its section 10 (zkwg_zkey_apply_delta) -> bytes"""
+    import numpy as np
+    lib = _lib.load()
+    a = np.frombuffer(zkey_bytes, dtype=np.uint8)      # (no copy; works for an mmap)
+    size, out_len = C.c_uint64(), C.c_uint64()
+    try:
+        rc = lib.zkwg_zkey_apply_delta_size(a.ctypes.data, a.size, len(section10), C.byref(size))
+        if rc == 0:
+            out = (C.c_uint8 * size.value)()
+            rc = lib.zkwg_zkey_apply_delta(device, a.ctypes.data, a.size, int(k % (1 << 256)).to_bytes(32, "little"), bytes(section10), len(section10), out, size.value,
+                                           C.byref(out_len))
+    finally:
+        del a                                          # (an mmap cannot be closed while a view of it lives, e.g. in a traceback)
+    if rc != 0:
+        _fail(lib, rc)
+    return bytes(memoryview(out)[:out_len.value])
+
+
+def last_stats():
+    """seconds and group operations of this thread's last apply_delta (zkwg_zkey_apply_delta_stats)"""
+    lib = _lib.load()
+    sec, ops = (C.c_double * 5)(), (C.c_uint64 * 4)()
+    lib.zkwg_zkey_apply_delta_stats(sec, ops)
+    names = ("parse_copy", "upload_check", "scale_c", "scale_h", "affine_download")
+    return {"seconds": dict(zip(names, sec)), "ops": {"c": {"add": ops[0], "dbl": ops[1]}, "h": {"add": ops[2], "dbl": ops[3]}}}
+
+
+# ---- the challenge point ------------------------------------------------------------------------------------------------------------------------
+def _f2_mul(a, b):
+    return ((a[0] * b[0] - a[1] * b[1]) % Q, (a[0] * b[1] + a[1] * b[0]) % Q)
+
+
+def _fq_sqrt(a):
+    s = pow(a, (Q + 1) // 4, Q)                      # q = 3 mod 4
+    return s if s * s % Q == a % Q else None
+
+
+def _f2_sqrt(a):
+    """a root of a in Fq2 = Fq[i] / (i^2 + 1), or None: through the norm a0^2 + a1^2, whose root exists in Fq when a is a square"""
+    a0, a1 = a
+    if a1 == 0:
+        s = _fq_sqrt(a0)
+        if s is not None:
+            return (s, 0)
+        return (0, _fq_sqrt(-a0 % Q))                # a0 is not a square, so -a0 is (-1 is not): (t i)^2 = -t^2 = a0
+    n = _fq_sqrt((a0 * a0 + a1 * a1) % Q)
+    if n is None:
+        return None
+    half = pow(2, -1, Q)
+    x0 = _fq_sqrt((a0 + n) * half % Q)
+    if x0 is None:
+        x0 = _fq_sqrt((a0 - n) * half % Q)
+    if x0 is None or x0 == 0:
+        return None
+    x = (x0, a1 * pow(2 * x0, -1, Q) % Q)
+    return x if _f2_mul(x, x) == (a0 % Q, a1 % Q) else None
+
+
+_B2 = _f2_mul((3, 0), (9 * pow(82, -1, Q) % Q, -pow(82, -1, Q) % Q))      # 3 / (9 + i) = 3 (9 - i) / 82
+
+
+def _mont(v):
+    return ((v << 256) % Q).to_bytes(32, "little")
+
+
+def challenge_g2(transcript, device=0):
+    """-> a point of G2 (128 bytes in the zkey's form) that only the transcript determines"""
+    for counter in range(1 << 16):
+        h = [hashlib.blake2b(TAG_G2 + bytes(transcript) + struct.pack("<IB", counter, half), digest_size=64).digest() for half in (0, 1)]
+        x = (int.from_bytes(h[0], "little") % Q, int.from_bytes(h[1], "little") % Q)
+        x3 = _f2_mul(_f2_mul(x, x), x)
+        y = _f2_sqrt(((x3[0] + _B2[0]) % Q, (x3[1] + _B2[1]) % Q))
+        if y is None:
+            continue
+        y = min(y, ((-y[0]) % Q, (-y[1]) % Q))       # (which root: the smaller pair)
+        p = scale_points(2, _mont(x[0]) + _mont(x[1]) + _mont(y[0]) + _mont(y[1]), COFACTOR_G2, device)
+        if any(p):
+            return p
+    raise Phase2Error("no challenge point found")
+
+
+# ---- contributions --------------------------------------------------------------------------------------------------------------------------------
+def _contribute(zkey_bytes, k, s, params, device):
+    from .prover import fixed_base
+    sec = zkey.sections(zkey_bytes)
+    if 2 not in sec or sec[2][1] < 84 + 576:
+        raise Phase2Error("not a groth16 .zkey (header)")
+    d1 = sec[2][0] + 84 + 384
+    delta1 = bytes(zkey_bytes[d1:d1 + 64])
+    circuit_hash, recs = read_contributions(zkey_bytes)
+    rec = dict(params)
+    rec["delta_after"] = scale_points(1, delta1, k, device)
+    g1 = bytes(fixed_base(device, 1, [s, s * k % R]).cpu().numpy())
+    rec["g1_s"], rec["g1_sx"] = g1[:64], g1[64:]
+    rec["transcript"] = hashlib.blake2b(circuit_hash + b"".join(r["raw"] for r in recs) + g1, digest_size=64).digest()
+    rec["g2_spx"] = scale_points(2, challenge_g2(rec["transcript"], device), k, device)
+    return apply_delta(zkey_bytes, k, pack_section10(circuit_hash, [r["raw"] for r in recs] + [pack_record(rec)]), device)
+
+
+def contribution_scalars(seed):
+    """-> (k, s): the contribution's secret and the random scalar of its proof of knowledge"""
+    return derive_scalar(seed), derive_scalar(seed, TAG_POK)
+
+
+def contribute(zkey_bytes, name, entropy=None, device=0, *, urandom=os.urandom):
+    """-> the key after one more contribution.  entropy: str or bytes mixed into the 64 random bytes; urandom: where those come from
+    (a test that must know k passes its own)"""
+    e = b"" if entropy is None else entropy.encode() if isinstance(entropy, str) else bytes(entropy)
+    k, s = contribution_scalars(urandom(64) + e)
+    return _contribute(zkey_bytes, k, s, {"name": name}, device)
+
+
+def beacon(zkey_bytes, name, beacon_hash, num_iterations_exp, device=0):
+    """-> the key after a beacon: a contribution whose scalar everyone can recompute from the public beacon_hash (bytes or hex)"""
+    bh = bytes.fromhex(beacon_hash) if isinstance(beacon_hash, str) else bytes(beacon_hash)
+    if not 0 < len(bh) <= 255 or not 10 <= num_iterations_exp <= 63:
+        raise Phase2Error("the beacon hash must be 1 .. 255 bytes and the exponent 10 .. 63")
+    k, s = contribution_scalars(beacon_seed(bh, num_iterations_exp))
+    return _contribute(zkey_bytes, k, s, {"name": name, "type": TYPE_BEACON, "num_iterations_exp": num_iterations_exp, "beacon_hash": bh}, device)
+
+
+def main(argv=None):
+    ap = argparse.ArgumentParser(description="phase 2 of the groth16 set-up: a contribution or a beacon on a .zkey")
+    sub = ap.add_subparsers(dest="cmd", required=True)
+    pc = sub.add_parser("contribute")
+    pb = sub.add_parser("beacon")
+    for p in (pc, pb):
+        p.add_argument("zkey_in")
+        p.add_argument("zkey_out")
+    pb.add_argument("beacon_hash")
+    pb.add_argument("num_iterations_exp", type=int)
+    pc.add_argument("--entropy")
+    for p in (pc, pb):
+        p.add_argument("--name", required=True)
+        p.add_argument("--device", type=int, default=0)
+    a = ap.parse_args(argv)
+    z, why = None, ""
+    with open(a.zkey_in, "rb") as f, mmap.mmap(f.fileno(), 0, access=mmap.ACCESS_READ) as mm:
+        try:
+            z = contribute(mm, a.name, a.entropy, a.device) if a.cmd == "contribute" else beacon(mm, a.name, a.beacon_hash, a.num_iterations_exp, a.device)
+        except ValueError as e:                        # (Phase2Error, and what the section walk of zkwg.zkey raises)
+            why = str(e)
+    if z is None:
+        print(f"no key: {why}", file=sys.stderr)
+        return 1
+    open(a.zkey_out, "wb").write(z)
+    return 0
+
+
+if __name__ == "__main__":
+    sys.exit(main())

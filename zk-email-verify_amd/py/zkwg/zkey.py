@@ -12,7 +12,7 @@ UNPINNED until a real file is read: the round trip write -> read is what the tes
     5  A: nVars G1                             value is the coefficient times R^2 (so that a Montgomery product with a standard-form witness
     6  B1: nVars G1                            value lands in Montgomery form); rows nConstraints + s = wire s of A are the public rows
     7  B2: nVars G2                        8  C: nVars - nPublic - 1 G1 (private wires)
-    9  H: domainSize G1                   10  contributions (64-byte hash, u32 count)
+    9  H: domainSize G1                   10  contributions (64-byte hash, u32 count, records: zkwg/phase2.py)
 Points: affine, little-endian Montgomery limbs, x | y (G2: x.c0 | x.c1 | y.c0 | y.c1), all zeros = infinity -- exactly the layout
 zkwg_msm_create* takes, so sections 5-9 are uploaded as they are.
 """
@@ -22,10 +22,8 @@ R = 2188824287183927522224640574525727508854836440041603434369820418657580849561
 Q = 21888242871839275222246405745257275088696311157297823662689037894645226208583
 
 
-def read_zkey(data, coeffs=True):
-    """-> dict: n_vars, n_public, domain_size, power, points alpha1 ... delta2 (bytes as stored), ic / a / b1 / b2 / c / h (bytes of the
-    whole section), coeffs = [(matrix, constraint, signal, coefficient)] (standard-form integers; [] with coeffs=False: section 4 of a
-    large key is tens of millions of Python tuples)"""
+def sections(data):
+    """the section walk of a "zkey" container -> {id: (offset of the payload, size)}"""
     if data[:4] != b"zkey":
         raise ValueError("not a .zkey file")
     version, nsec = struct.unpack_from("<II", data, 4)
@@ -40,6 +38,14 @@ def read_zkey(data, coeffs=True):
             raise ValueError(f".zkey: section {sid} runs past the end of the file")
         sec[sid] = (pos + 12, size)
         pos += 12 + size
+    return sec
+
+
+def read_zkey(data, coeffs=True):
+    """-> dict: n_vars, n_public, domain_size, power, points alpha1 ... delta2 (bytes as stored), ic / a / b1 / b2 / c / h (bytes of the
+    whole section), section10 (its payload, b"" when absent), coeffs = [(matrix, constraint, signal, coefficient)] (standard-form
+    integers; [] with coeffs=False: section 4 of a large key is tens of millions of Python tuples)"""
+    sec = sections(data)
     for need in (1, 2, 3, 5, 6, 7, 8, 9):
         if need not in sec:
             raise ValueError(f".zkey: section {need} is missing")
@@ -68,6 +74,7 @@ def read_zkey(data, coeffs=True):
         if size != want[sid]:
             raise ValueError(f".zkey: section {sid} holds {size} bytes, expected {want[sid]}")
         out[name] = bytes(data[o:o + size])
+    out["section10"] = bytes(data[sec[10][0]:sec[10][0] + sec[10][1]]) if 10 in sec else b""
     out["coeffs"] = []
     if 4 in sec and coeffs:
         o, _ = sec[4]
@@ -82,8 +89,9 @@ def read_zkey(data, coeffs=True):
     return out
 
 
-def write_zkey(n_vars, n_public, domain_size, points, ic, a, b1, b2, c, h, coeffs=()):
-    """points: dict alpha1, beta1, beta2, gamma2, delta1, delta2 (bytes as stored); ic ... h: bytes of the sections; coeffs as read_zkey gives"""
+def write_zkey(n_vars, n_public, domain_size, points, ic, a, b1, b2, c, h, coeffs=(), section10=None):
+    """points: dict alpha1, beta1, beta2, gamma2, delta1, delta2 (bytes as stored); ic ... h: bytes of the sections; coeffs as read_zkey
+    gives; section10: the payload of section 10 (None: 64 zero bytes and a count of 0, a key without contributions)"""
     assert len(ic) == 64 * (n_public + 1) and len(a) == 64 * n_vars and len(b1) == 64 * n_vars and len(b2) == 128 * n_vars
     assert len(c) == 64 * (n_vars - n_public - 1) and len(h) == 64 * domain_size
     r2 = pow(1 << 256, 2, R)
@@ -92,7 +100,8 @@ def write_zkey(n_vars, n_public, domain_size, points, ic, a, b1, b2, c, h, coeff
         assert len(points[name]) == size
         hdr += points[name]
     s4 = struct.pack("<I", len(coeffs)) + b"".join(struct.pack("<III", m, cc, s) + (v * r2 % R).to_bytes(32, "little") for m, cc, s, v in coeffs)
-    secs = [(1, struct.pack("<I", 1)), (2, hdr), (3, ic), (4, s4), (5, a), (6, b1), (7, b2), (8, c), (9, h), (10, bytes(64) + struct.pack("<I", 0))]
+    secs = [(1, struct.pack("<I", 1)), (2, hdr), (3, ic), (4, s4), (5, a), (6, b1), (7, b2), (8, c), (9, h),
+            (10, bytes(64) + struct.pack("<I", 0) if section10 is None else bytes(section10))]
     out = [b"zkey", struct.pack("<II", 1, len(secs))]
     for sid, payload in secs:
         out.append(struct.pack("<IQ", sid, len(payload)))
