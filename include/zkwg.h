@@ -603,7 +603,8 @@ int zkwg_expand_full_host(const zkwg_circuit_t* c, const uint8_t* packed_inputs,
  * `snarkjs groth16 setup circuit.r1cs pot.ptau circuit.zkey`): a compiler-format .r1cs and a PREPARED powers-of-tau file give the
  * initial key (gamma = delta = 1, no contributions) as a .zkey that zkwg_prover_create_zkey / zkwg_prover_create_wtns and snarkjs'
  * provers read.  Section 10 is 64 zero bytes and a count of 0 (the circuit hash is not computed: `snarkjs zkey verify` refuses the
- * file, no prover looks there).  Preparing an unprepared file, chunked keys and other curves are not built; phase 2: below.
+ * file, no prover looks there).  An unprepared file is prepared by zkwg_ptau_prepare (below); chunked keys and other curves are not
+ * built; phase 2: below.
  *
  * zkwg_setup_slices: the points the set-up reads, in the zkey's form (affine, little-endian Montgomery words, zeros = infinity), for
  * the circuit's domain 2^power: [L_j(tau)]_1, [L_j(tau)]_2, [alpha L_j(tau)]_1, [beta L_j(tau)]_1 (2^power points each) and
@@ -663,6 +664,39 @@ int zkwg_zkey_apply_delta(int device, const uint8_t* zkey, uint64_t len, const u
  * sections, upload + curve check, scaling of section 8, scaling of section 9, conversion + download}; {mixed additions, doublings} of
  * section 8, then of section 9 */
 void zkwg_zkey_apply_delta_stats(double seconds[5], uint64_t ops[4]);
+
+/* ---- prepare phase 2: the Lagrange sections of a powers-of-tau file on the device (csrc/zkwg_ptau_core.h) -------
+ * `snarkjs powersoftau prepare phase2 pot.ptau pot_final.ptau`, the step between a ceremony file and zkwg_ptau_parse / zkwg_zkey_new
+ * (docs/zk-email-docs/UsageGuide/README.md:145-180 names the prepared file).  Not built: powersoftau new / contribute / beacon / verify.
+ *
+ * zkwg_group_ntt_device: the discrete Fourier transform of 2^log2_n affine points in the zkey's form (64 / 128 bytes, little-endian
+ * Montgomery words, zeros = infinity; group 1 / 2; a device pointer, 16-byte aligned), IN PLACE, natural order in and out:
+ *   inverse = 0:  out[j] = sum_k w^(jk) in[k]          inverse = 1:  out[j] = 2^-log2_n sum_k w^(-jk) in[k]
+ * w: the 2^log2_n-th root of unity of zkwg_ntt_* (ffjavascript's Fr.w[log2_n]).  Points at infinity among the inputs, and equal or
+ * opposite points meeting inside a butterfly, are computed, not excluded.  Every input point is checked first (words below q, on its
+ * curve); one that fails refuses the whole call and leaves the points as they were: ZKWG_RC_BAD_CONFIG, zkwg_last_error says "curve".
+ * There is NO subgroup check of G2 points (the set-up makes none either): points of the twist outside the subgroup of order r are
+ * transformed as elements of the whole curve group only as far as w^k acts on them as an integer, which is not a transform.
+ * The call allocates 312 (G1) / 520 (G2) bytes per point, works on hip_stream, synchronises it and frees its buffers before it
+ * returns.  log2_n above 29 (G1: 168 GB) / 28 (G2: 140 GB) is refused with a message.
+ *
+ * zkwg_ptau_prepare: the file operation, host memory in and out (an mmap: only the prefixes the output needs are read).  power = 0:
+ * the file's own power; 0 < power < the file's: the output is a file of that power (header power set, ceremonyPower kept, sections
+ * 2 - 6 cut to 2 n - 1 | n | n | n | 1 points, n = 2^power, section 7 verbatim); above the file's: refused.  Output: sections 1 - 7,
+ * then 12, 13, 14, 15 as zkwg_ptau_parse reads them: level q at point 2^q - 1, q = 0 .. power, section 12 one level more.  Level
+ * q <= power is the inverse transform of the first 2^q points of section 2 / 3 / 4 / 5; level power + 1 of section 12 is the inverse
+ * transform of the 2 n - 1 points of section 2 followed by ONE POINT AT INFINITY (tau^(2 n - 1) is not in a file of that power), also
+ * when `power` cuts a larger file.  Refused (ZKWG_RC_BAD_CONFIG + zkwg_last_error): whatever the section walker refuses (sizes are
+ * checked before any read), a file that has a section 12 - 15 ("already prepared"), a point of sections 2 - 5 that is not on its curve
+ * or not reduced.  out: cap >= what zkwg_ptau_prepare_size gives for the same power.  Device memory: 376 bytes per point of the
+ * largest level (2^(power + 1) G1 points; G2: 648 x 2^power) and 64 bytes per table entry (2^power). */
+int zkwg_group_ntt_device(int device, int group, void* d_points, uint32_t log2_n, int inverse, void* hip_stream);
+int zkwg_ptau_prepare_size(const uint8_t* ptau, uint64_t len, uint32_t power, uint64_t* out_bytes);
+int zkwg_ptau_prepare(int device, const uint8_t* ptau, uint64_t len, uint32_t power, uint8_t* out, uint64_t cap, uint64_t* out_len);
+/* seconds and group operations of the last zkwg_ptau_prepare of this thread (tools/bench_ptau.py): per section 12, 13, 14, 15
+ * {upload + curve check, transforms up to the last stage's butterflies, last conversion + download} (12 values), then per section 32
+ * values: the transform's seconds of level q at 12 + 32 * section + q; ops: per section {additions, doublings} */
+void zkwg_ptau_prepare_stats(double seconds[140], uint64_t ops[8]);
 
 /* ---- the compact image as a device-side interchange format --------------------------
  * zkwg_prepare_device leaves, per email, a compact IMAGE in the scratch buffer (~0.45 MB instead of the 57 MB

@@ -58,7 +58,8 @@ struct ZkPtauFile {
   u32 power, ceremony_power;
 };
 static inline int zk_ptau_fail(std::string& err, const char* m) { err = m; return ZKWG_RC_BAD_CONFIG; }
-static inline int zk_ptau_sections(const u8* p, u64 len, ZkPtauFile& F, std::string& err) {
+// need_lagrange = false: the walk of an UNPREPARED file (zkwg_ptau_core.h); sections 12 - 15 are then recorded if present, not checked
+static inline int zk_ptau_sections(const u8* p, u64 len, ZkPtauFile& F, std::string& err, bool need_lagrange = true) {
   for (int i = 0; i < 16; ++i) F.off[i] = F.size[i] = 0;
   if (!p || len < 12 || memcmp(p, "ptau", 4) != 0) return zk_ptau_fail(err, "not a .ptau file (magic)");
   u32 version, nsec;
@@ -85,6 +86,7 @@ static inline int zk_ptau_sections(const u8* p, u64 len, ZkPtauFile& F, std::str
   const u64 want[7] = {0, 0, (2 * n - 1) * 64, n * 128, n * 64, n * 64, 128};
   for (int id = 2; id <= 6; ++id)
     if (!F.off[id] || F.size[id] != want[id]) return zk_ptau_fail(err, ".ptau: a point section (2 - 6) is missing or of the wrong size");
+  if (!need_lagrange) return ZKWG_RC_OK;
   for (const ZkPtauSection& s : ZK_PTAU_LAGRANGE)
     if (!F.off[s.id]) return zk_ptau_fail(err, "Powers of tau is not prepared");
   for (const ZkPtauSection& s : ZK_PTAU_LAGRANGE)

@@ -105,7 +105,8 @@ def main(argv=None):
         try:
             z = new_zkey(r1cs, mm, device=a.device)
         except SetupError as e:
-            print(f"no key: {e}", file=sys.stderr)
+            hint = " (run `python -m zkwg.ptau prepare` on the file first)" if "not prepared" in str(e) else ""
+            print(f"no key: {e}{hint}", file=sys.stderr)
             return 1
     open(a.zkey, "wb").write(z)
     if a.verification_key_json:
