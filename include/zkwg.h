@@ -667,7 +667,7 @@ void zkwg_zkey_apply_delta_stats(double seconds[5], uint64_t ops[4]);
 
 /* ---- prepare phase 2: the Lagrange sections of a powers-of-tau file on the device (csrc/zkwg_ptau_core.h) -------
  * `snarkjs powersoftau prepare phase2 pot.ptau pot_final.ptau`, the step between a ceremony file and zkwg_ptau_parse / zkwg_zkey_new
- * (docs/zk-email-docs/UsageGuide/README.md:145-180 names the prepared file).  Not built: powersoftau new / contribute / beacon / verify.
+ * (docs/zk-email-docs/UsageGuide/README.md:145-180 names the prepared file).  powersoftau new / contribute / beacon: the next block.  Not built: powersoftau verify.
  *
  * zkwg_group_ntt_device: the discrete Fourier transform of 2^log2_n affine points in the zkey's form (64 / 128 bytes, little-endian
  * Montgomery words, zeros = infinity; group 1 / 2; a device pointer, 16-byte aligned), IN PLACE, natural order in and out:
@@ -697,6 +697,44 @@ int zkwg_ptau_prepare(int device, const uint8_t* ptau, uint64_t len, uint32_t po
  * {upload + curve check, transforms up to the last stage's butterflies, last conversion + download} (12 values), then per section 32
  * values: the transform's seconds of level q at 12 + 32 * section + q; ops: per section {additions, doublings} */
 void zkwg_ptau_prepare_stats(double seconds[140], uint64_t ops[8]);
+
+/* ---- powers of tau: a contribution on the device (csrc/zkwg_ptau_key_core.h) --------------------------------
+ * `snarkjs powersoftau contribute` / `beacon` on an UNPREPARED file, and the primitive underneath: many points, each times its own
+ * scalar.  (`powersoftau new` needs no device: zkwg/ptau.py writes the generators.)  The record of section 7 -- who contributed, the
+ * proofs of knowledge, the challenge chain -- is the host layer's (zkwg/ptau.py) and is ZKWG'S OWN: `snarkjs powersoftau verify` does
+ * NOT accept the file; `prepare`, `setup` and every reader of the points do.  Not built: powersoftau verify (pairings in product code),
+ * snarkjs-compatible challenge hashes, import / export challenge.
+ *
+ * zkwg_point_mul_device: d_out[i] = scalars[i] * d_points[i] for n affine points in the zkey's form (64 / 128 bytes, little-endian
+ * Montgomery words, zeros = infinity and stay zeros; group 1 / 2; device pointers, 16-byte aligned; d_out may be d_points).
+ * d_scalars: n x 32 bytes on the device, 16-byte aligned, little-endian, standard form, below r (a value at or above r is reduced
+ * modulo r; 0 gives infinity).  zkwg_point_powers_device: the scalar of point i is c * t^(first + i) mod r, computed per lane on the
+ * device from a table of t^(2^j) -- no scalar array crosses to the device.  c, t: 32 bytes, little-endian, reduced modulo r by the call;
+ * either = 0 mod r is refused (ZKWG_RC_BAD_CONFIG), first + n must not pass 2^64 (ZKWG_RC_BAD_ARG).
+ * Both: EVERY point is checked first (words below q, on its curve); one that fails refuses the whole call and leaves the points as they
+ * were: ZKWG_RC_BAD_CONFIG, zkwg_last_error says "curve".  There is NO subgroup check of G2 points: a twist point outside the subgroup
+ * of order r is multiplied by the integer scalars[i] (point_mul); the result of point_powers is unspecified for it.  The walk is a
+ * regular signed window of 4 bits over a per-point table of 8 affine odd multiples in device memory: the calls allocate 2,024 (G1) /
+ * 3,544 (G2) bytes per point for at most 2^20 (G1) / 2^19 (G2) points at a time, work on hip_stream, synchronise it and free their
+ * buffers before they return.
+ *
+ * zkwg_ptau_apply_key: the file operation, host memory in and out.  Point k of sections 2 and 3 times tau^k (2 n - 1 G1 and n G2
+ * points, n = 2^power), of section 4 times alpha tau^k, of section 5 times beta tau^k, the point of section 6 times beta
+ * (zkwg_point_scale_device); section 1 is copied, section7 is the payload the new file gets as its section 7, verbatim.  The sections are
+ * written in the order 1 .. 7.  tau, alpha, beta: 32 bytes, little-endian, reduced modulo r by the call.  Refused (ZKWG_RC_BAD_CONFIG +
+ * zkwg_last_error; the bytes of `out` are unspecified then): whatever the section walker refuses (sizes are checked before any read), a
+ * file that has a section 12 - 15 ("already prepared": its Lagrange sections would go stale), tau, alpha or beta = 0 mod r, a point of
+ * sections 2 - 6 that is not on its curve or not reduced.  out: cap >= what zkwg_ptau_apply_key_size gives for the same section7_len. */
+int zkwg_point_mul_device(int device, int group, const void* d_points, uint64_t n, const void* d_scalars, void* d_out, void* hip_stream);
+int zkwg_point_powers_device(int device, int group, const void* d_points, uint64_t n, const uint8_t* c, const uint8_t* t, uint64_t first,
+                             void* d_out, void* hip_stream);
+int zkwg_ptau_apply_key_size(const uint8_t* ptau, uint64_t len, uint64_t section7_len, uint64_t* out_bytes);
+int zkwg_ptau_apply_key(int device, const uint8_t* ptau, uint64_t len, const uint8_t* tau, const uint8_t* alpha, const uint8_t* beta,
+                        const uint8_t* section7, uint64_t section7_len, uint8_t* out, uint64_t cap, uint64_t* out_len);
+/* seconds and group operations of the last zkwg_ptau_apply_key of this thread (tools/bench_ptau_contribute.py): per section 2, 3, 4, 5
+ * {upload + curve check, tables (odd multiples, made affine), walk, conversion + download} (16 values), [16] parse + copy of sections 1
+ * and 7, [17] section 6; ops: per section {additions, doublings} */
+void zkwg_ptau_apply_key_stats(double seconds[18], uint64_t ops[8]);
 
 /* ---- the compact image as a device-side interchange format --------------------------
  * zkwg_prepare_device leaves, per email, a compact IMAGE in the scratch buffer (~0.45 MB instead of the 57 MB

@@ -32,6 +32,7 @@
 // but the window's table is 4 x 144 bytes a lane = 36 KB a wavefront (G2: 72 KB): with 160 KB of LDS a compute unit that is ONE wavefront
 // per SIMD, and three per SIMD (what zk_phase2_scale<G1> runs at, and the chain of dependent products needs to hide its latency) leave
 // 213 bytes a lane -- not two entries.  So the distinct-scalar share is predicated digits; it is 6 of the L - 1 multiplying stages.
+// (Where EVERY multiplication has its own scalar -- a contribution to the file -- the table goes to device memory instead: zkwg_ptau_key_core.h.)
 // A row/column split would leave ONE distinct pass instead of six (and fold 2^-L into it): predicted (L - 0.8) / (L + 3.5) of this
 // schedule's products at large L (0.82 at L = 21).  Not built.
 //

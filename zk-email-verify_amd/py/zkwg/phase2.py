@@ -81,6 +81,31 @@ def _pack_params(rec):
     return out
 
 
+def unpack_params(data, p, end, where, error=None):
+    """the tagged parameters at data[p:end] -> {field: value} (what _pack_params wrote); `where` names the section in a refusal"""
+    error = error or Phase2Error
+    by_tag = {tag: (field, kind) for tag, field, kind in PARAMS}
+    out = {}
+    while p < end:
+        if data[p] not in by_tag or p + 2 > end:
+            raise error(f"{where}: unknown or truncated parameter")
+        field, kind = by_tag[data[p]]
+        if kind == "u8":
+            out[field] = data[p + 1]
+            p += 2
+        else:
+            ln = data[p + 1]
+            if p + 2 + ln > end:
+                raise error(f"{where}: truncated parameter")
+            v = bytes(data[p + 2:p + 2 + ln])
+            out[field] = v.decode() if kind == "str" else v
+            p += 2 + ln
+    return out
+
+
+pack_params = _pack_params      # (zkwg/ptau.py writes the same tagged parameters)
+
+
 def pack_record(rec):
     out = b"".join(rec[name] for name, _ in RECORD_POINTS)
     assert len(out) == sum(size for _, size in RECORD_POINTS) and len(rec["transcript"]) == 64
@@ -101,7 +126,6 @@ def read_contributions(zkey_or_section10):
         raise Phase2Error("section 10 is shorter than its hash and count")
     n = struct.unpack_from("<I", data, 64)[0]
     pos, recs = 68, []
-    by_tag = {tag: (field, kind) for tag, field, kind in PARAMS}
     fixed = sum(size for _, size in RECORD_POINTS) + 64 + 4
     for _ in range(n):
         if pos + fixed > len(data):
@@ -115,21 +139,8 @@ def read_contributions(zkey_or_section10):
         pos += 68
         if pos + plen > len(data):
             raise Phase2Error("section 10: the parameters of a record run past the end of the section")
-        p, end = pos, pos + plen
-        while p < end:
-            if data[p] not in by_tag or p + 2 > end:
-                raise Phase2Error("section 10: unknown or truncated parameter")
-            field, kind = by_tag[data[p]]
-            if kind == "u8":
-                rec[field] = data[p + 1]
-                p += 2
-            else:
-                ln = data[p + 1]
-                if p + 2 + ln > end:
-                    raise Phase2Error("section 10: truncated parameter")
-                v = bytes(data[p + 2:p + 2 + ln])
-                rec[field] = v.decode() if kind == "str" else v
-                p += 2 + ln
+        end = pos + plen
+        rec.update(unpack_params(data, pos, end, "section 10"))
         pos = end
         rec["raw"] = bytes(data[start:pos])
         recs.append(rec)
