@@ -667,7 +667,7 @@ void zkwg_zkey_apply_delta_stats(double seconds[5], uint64_t ops[4]);
 
 /* ---- prepare phase 2: the Lagrange sections of a powers-of-tau file on the device (csrc/zkwg_ptau_core.h) -------
  * `snarkjs powersoftau prepare phase2 pot.ptau pot_final.ptau`, the step between a ceremony file and zkwg_ptau_parse / zkwg_zkey_new
- * (docs/zk-email-docs/UsageGuide/README.md:145-180 names the prepared file).  powersoftau new / contribute / beacon: the next block.  Not built: powersoftau verify.
+ * (docs/zk-email-docs/UsageGuide/README.md:145-180 names the prepared file).  powersoftau new / contribute / beacon: the next block; powersoftau verify: the one after.
  *
  * zkwg_group_ntt_device: the discrete Fourier transform of 2^log2_n affine points in the zkey's form (64 / 128 bytes, little-endian
  * Montgomery words, zeros = infinity; group 1 / 2; a device pointer, 16-byte aligned), IN PLACE, natural order in and out:
@@ -702,8 +702,8 @@ void zkwg_ptau_prepare_stats(double seconds[140], uint64_t ops[8]);
  * `snarkjs powersoftau contribute` / `beacon` on an UNPREPARED file, and the primitive underneath: many points, each times its own
  * scalar.  (`powersoftau new` needs no device: zkwg/ptau.py writes the generators.)  The record of section 7 -- who contributed, the
  * proofs of knowledge, the challenge chain -- is the host layer's (zkwg/ptau.py) and is ZKWG'S OWN: `snarkjs powersoftau verify` does
- * NOT accept the file; `prepare`, `setup` and every reader of the points do.  Not built: powersoftau verify (pairings in product code),
- * snarkjs-compatible challenge hashes, import / export challenge.
+ * NOT accept the file; `prepare`, `setup` and every reader of the points do -- and `python -m zkwg.ptau verify` checks it (the next
+ * block).  Not built: snarkjs-compatible challenge hashes, import / export challenge, `zkey verify`.
  *
  * zkwg_point_mul_device: d_out[i] = scalars[i] * d_points[i] for n affine points in the zkey's form (64 / 128 bytes, little-endian
  * Montgomery words, zeros = infinity and stay zeros; group 1 / 2; device pointers, 16-byte aligned; d_out may be d_points).
@@ -735,6 +735,34 @@ int zkwg_ptau_apply_key(int device, const uint8_t* ptau, uint64_t len, const uin
  * {upload + curve check, tables (odd multiples, made affine), walk, conversion + download} (16 values), [16] parse + copy of sections 1
  * and 7, [17] section 6; ops: per section {additions, doublings} */
 void zkwg_ptau_apply_key_stats(double seconds[18], uint64_t ops[8]);
+
+/* ---- powers of tau: verification (csrc/zkwg_verify_core.h, csrc/zkwg_pairing.h) -------------------------------------
+ * What `python -m zkwg.ptau verify` (zkwg/ptau.py) is made of: the sections' millions of points are tested and folded on the device, the
+ * few dozen pairings over the folded points run on the HOST, once.
+ *
+ * zkwg_pairing_check: is_one = (prod_i e(g1[i], g2[i]) == 1), BN254 optimal ate, one Miller loop per pair and ONE final exponentiation per
+ * call.  Points in the zkey's form (64 / 128 bytes, Montgomery words, zeros = infinity: that pair contributes 1).  Refused with
+ * ZKWG_RC_BAD_CONFIG + zkwg_last_error: a word >= q or a point off its curve ("curve"), a G2 point outside the subgroup of order r
+ * ("subgroup": the criterion below, host build).  No device.
+ *
+ * zkwg_g2_subgroup_device: n affine G2 points in the zkey's form on the device (16-byte aligned).  *n_bad = how many are outside the
+ * subgroup of order r, *first_bad = the lowest such index (unchanged when none).  Infinity counts as inside.  Every point is
+ * curve-checked first as in zkwg_point_scale_device (one that fails refuses the call, "curve").  Criterion [EXT: El Housni, Guillevic,
+ * Piellard]: with A = [u] Q, Q is in G2 iff A + Q + psi(A) + psi^2(A) = psi^3([2] A) -- 63 doublings instead of the 254 of [r] Q.
+ * Pieces of at most 2^20 points (128 bytes of device memory a point); the call synchronises and frees what it allocated.
+ *
+ * zkwg_point_rlc_device: out_a = sum_i s_i A_i, out_b = sum_i s_i B_i over n points of one group (1 / 2); s_i: n x 16 bytes on the
+ * device, little-endian (any 128-bit value).  d_b may be NULL (one sum; out_b is not written) and may overlap d_a -- d_b = d_a + one
+ * point is the shifted form the powers checks need.  Outputs: host memory, the zkey's form, zeros = infinity.  Curve check of every
+ * point of both arrays first, refusal as above.  piece_points = 0: 2^22; every piece is one multi-exponentiation plan in the classic
+ * layout, and the partial sums of the pieces are added on the host.  zkwg_point_rlc32_device: the same with 32-byte scalars, standard
+ * form, BELOW r (the plans' rule). */
+int zkwg_pairing_check(const uint8_t* g1, const uint8_t* g2, uint32_t n, int* is_one);
+int zkwg_g2_subgroup_device(int device, const void* d_points, uint64_t n, uint64_t* n_bad, uint64_t* first_bad, void* hip_stream);
+int zkwg_point_rlc_device(int device, int group, const void* d_a, const void* d_b, uint64_t n, const void* d_scalars, uint64_t piece_points,
+                          uint8_t* out_a, uint8_t* out_b, void* hip_stream);
+int zkwg_point_rlc32_device(int device, int group, const void* d_a, const void* d_b, uint64_t n, const void* d_scalars, uint64_t piece_points,
+                            uint8_t* out_a, uint8_t* out_b, void* hip_stream);
 
 /* ---- the compact image as a device-side interchange format --------------------------
  * zkwg_prepare_device leaves, per email, a compact IMAGE in the scratch buffer (~0.45 MB instead of the 57 MB

@@ -197,6 +197,10 @@ def load():
         "zkwg_ptau_apply_key_size": (i32, [vp, u64, u64, C.POINTER(u64)]),
         "zkwg_ptau_apply_key": (i32, [i32, vp, u64, vp, vp, vp, vp, u64, vp, u64, C.POINTER(u64)]),
         "zkwg_ptau_apply_key_stats": (None, [C.POINTER(C.c_double), C.POINTER(u64)]),
+        "zkwg_pairing_check": (i32, [vp, vp, u32, C.POINTER(C.c_int)]),
+        "zkwg_g2_subgroup_device": (i32, [i32, vp, u64, C.POINTER(u64), C.POINTER(u64), vp]),
+        "zkwg_point_rlc_device": (i32, [i32, i32, vp, vp, u64, vp, u64, vp, vp, vp]),
+        "zkwg_point_rlc32_device": (i32, [i32, i32, vp, vp, u64, vp, u64, vp, vp, vp]),
         "zkwg_groth16_assemble": (i32, [vp] * 15),
         "zkwg_calculate_batch_resident": (i32, [vp, vp, u64, vp, vp, u64, u64, vp, vp]),
         "zkwg_resident_placement": (i32, [vp, C.POINTER(C.c_float), i32, C.POINTER(C.c_int)]),
@@ -227,4 +231,5 @@ EXPORTS = [
     "zkwg_point_scale_device", "zkwg_zkey_apply_delta_size", "zkwg_zkey_apply_delta", "zkwg_zkey_apply_delta_stats",
     "zkwg_group_ntt_device", "zkwg_ptau_prepare_size", "zkwg_ptau_prepare", "zkwg_ptau_prepare_stats",
     "zkwg_point_mul_device", "zkwg_point_powers_device", "zkwg_ptau_apply_key_size", "zkwg_ptau_apply_key", "zkwg_ptau_apply_key_stats",
+    "zkwg_pairing_check", "zkwg_g2_subgroup_device", "zkwg_point_rlc_device", "zkwg_point_rlc32_device",
 ]

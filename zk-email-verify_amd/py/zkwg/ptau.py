@@ -3,6 +3,7 @@ python -m zkwg.ptau contribute in.ptau out.ptau --name N [--entropy E] [--device
 python -m zkwg.ptau beacon in.ptau out.ptau HASHHEX EXP --name N [--device D]
 python -m zkwg.ptau prepare in.ptau out.ptau [--power P] [--device D]
 python -m zkwg.ptau info file.ptau
+python -m zkwg.ptau verify file.ptau [--device D]
 -- snarkjs `.ptau` (powers of tau) reader / writer and `snarkjs powersoftau prepare phase2` on the device: the ceremony file `groth16 setup` takes its points from (reference workflow:
 docs/zk-email-docs/UsageGuide/README.md:145-180, the prepared `powersOfTau28_hez_final_NN.ptau` files).
 
@@ -39,7 +40,13 @@ RECORD_POINTS -- the five points after the contribution, then per secret x of ta
 zkwg.phase2.PARAMS.  The first challenge of a file without contributions is BLAKE2b-512(its sections 2 - 6).
 THE CHALLENGE CHAIN AND THE CHALLENGE POINT ARE ZKWG'S OWN (zkwg.phase2.challenge_g2: snarkjs' ChaCha stream cannot be restated
 offline), so `snarkjs powersoftau verify` does NOT accept the file; `prepare`, `setup` and everything else that reads the points do.
-Not built: powersoftau verify, import / export challenge."""
+
+`verify` CHECKS A FILE END TO END, in either state and at any point of the workflow: every point reduced and on its curve, every G2 point
+of sections 3, 6, 13 in the subgroup of order r (zkwg_g2_subgroup_device), the sections powers of ONE tau (and alpha, beta times them),
+every record's proofs of knowledge and its link to the record before, the challenge chain's last link, and the Lagrange sections against
+the powers.  A section of 2^21 points becomes the four points of one pairing check by a random linear combination on the device
+(zkwg_point_rlc_device); the pairings themselves, a few dozen, run on the host (zkwg.pairing).  See `verify` below for the checks.
+Not built: snarkjs-compatible challenge hashes, import / export challenge, `zkey verify`."""
 import argparse
 import ctypes as C
 import hashlib
@@ -437,8 +444,265 @@ def group_ntt(group, points, inverse, device=0):
     return bytes(d.cpu().numpy())
 
 
+# ---- verify ---------------------------------------------------------------------------------------------------------------------------------------
+POWERS = {2: 1, 3: 2, 4: 1, 5: 1}                  # section -> group
+LAGRANGE_OF = {12: 2, 13: 3, 14: 4, 15: 5}         # Lagrange section -> the section of its powers
+_W28 = pow(5, (R - 1) >> 28, R)                    # ffjavascript's Fr.w[28]; w[q] = w[q + 1]^2
+NTT_MIN_LOG2 = 2                                   # the smallest domain of zkwg_ntt_create
+
+
+class _Device:
+    """the device calls of `verify` over torch tensors (the CPU tests put host mirrors in its place)"""
+
+    def __init__(self, device):
+        import torch
+        from . import _lib
+        self.device, self.torch, self.lib = device, torch, _lib.load()
+        self.dev = torch.device("cuda", device)
+
+    def upload(self, data):
+        return self.torch.frombuffer(bytearray(data), dtype=self.torch.uint8).to(self.dev)
+
+    def g2_subgroup(self, points, n):
+        """-> (points outside the subgroup, the lowest index of one or None)"""
+        n_bad, first = C.c_uint64(), C.c_uint64()
+        rc = self.lib.zkwg_g2_subgroup_device(self.device, points.data_ptr(), n, C.byref(n_bad), C.byref(first), 0)
+        if rc != 0:
+            _fail(self.lib, rc)
+        return n_bad.value, (first.value if n_bad.value else None)
+
+    def rlc(self, group, points, first, n, scalars, wide=False, shifted=False, piece=0):
+        """sum_i s_i P[first + i], i < n -> (sum, None); shifted: also sum_i s_i P[first + i + 1] from the same upload.  scalars: n x 16
+        bytes on the device (wide: n x 32, below r)"""
+        pt = 64 if group == 1 else 128
+        a = points.data_ptr() + first * pt
+        out_a, out_b = (C.c_uint8 * pt)(), (C.c_uint8 * pt)()
+        fn = self.lib.zkwg_point_rlc32_device if wide else self.lib.zkwg_point_rlc_device
+        rc = fn(self.device, group, a, a + pt if shifted else None, n, scalars.data_ptr(), piece, out_a, out_b if shifted else None, 0)
+        if rc != 0:
+            _fail(self.lib, rc)
+        return bytes(out_a), (bytes(out_b) if shifted else None)
+
+    def ifft(self, scalars16, q):
+        """2^q 16-byte values (bytes) -> their inverse field transform over the 2^q-th roots, 32-byte values on the device"""
+        import numpy as np
+        n = 1 << q
+        wide = np.zeros((n, 32), dtype=np.uint8)
+        wide[:, :16] = np.frombuffer(scalars16, dtype=np.uint8).reshape(n, 16)
+        d = self.torch.from_numpy(wide.reshape(-1)).to(self.dev)
+        plan = C.c_void_p()
+        rc = self.lib.zkwg_ntt_create(self.device, q, C.byref(plan))
+        if rc == 0:
+            # (the transform is linear and its tables carry the Montgomery factor: standard-form values in, standard-form values out)
+            rc = self.lib.zkwg_ntt_transform_device(plan, d.data_ptr(), 1, 1, 0)
+            self.lib.zkwg_ntt_destroy(plan)
+        if rc != 0:
+            _fail(self.lib, rc)
+        return d
+
+
+def _backend(device):
+    return _Device(device)
+
+
+def g2_subgroup(points, device=0):
+    """128-byte G2 points (bytes in the zkey's form) -> (how many are outside the subgroup of order r, the lowest index of one or None)
+    (zkwg_g2_subgroup_device)"""
+    if len(points) % 128:
+        raise PtauError("the points must be whole")
+    B = _backend(device)
+    return B.g2_subgroup(B.upload(points), len(points) // 128) if points else (0, None)
+
+
+def rlc(group, points, scalars, shifted=False, wide=False, piece=0, device=0):
+    """sum_i s_i P_i for points and 16-byte scalars as bytes (wide: 32-byte scalars below r) -> the point in the zkey's form
+    (zkwg_point_rlc_device).  shifted: one point more than scalars; -> (sum_i s_i P_i, sum_i s_i P_(i+1)) from ONE array on the device"""
+    pt, sb = (64 if group == 1 else 128), (32 if wide else 16)
+    n = len(scalars) // sb
+    if len(scalars) != n * sb or len(points) != (n + (1 if shifted else 0)) * pt or n == 0:
+        raise PtauError("one scalar per whole point (and one point more in the shifted form)")
+    B = _backend(device)
+    out = B.rlc(group, B.upload(points), 0, n, B.upload(scalars), wide=wide, shifted=shifted, piece=piece)
+    return out if shifted else out[0]
+
+
+def ifft_host(values, q):
+    """the inverse transform of 2^q integers by the definition: out[k] = 2^-q sum_j values[j] w^(-j k), w = Fr.w[q]"""
+    n = 1 << q
+    w_inv = pow(pow(_W28, 1 << (28 - q), R), -1, R)
+    n_inv = pow(n, -1, R)
+    return [n_inv * sum(v * pow(w_inv, j * k, R) for j, v in enumerate(values)) % R for k in range(n)]
+
+
+def new_challenge(power):
+    """BLAKE2b-512 of sections 2 - 6 of new(power), streamed (the file itself is 2^power x 384 bytes)"""
+    n, (g1, g2) = 1 << power, generators()
+    h = hashlib.blake2b(digest_size=64)
+    for point, count in ((g1, 2 * n - 1), (g2, n), (g1, n), (g1, n), (g2, 1)):
+        block = point * min(count, 1 << 14)
+        for _ in range(count // (1 << 14)):
+            h.update(block)
+        h.update(point * (count % (1 << 14)))
+    return h.digest()
+
+
+def _has_infinity(view, pt):
+    import numpy as np
+    a = np.frombuffer(view, dtype=np.uint8).reshape(-1, pt)
+    return bool((~a.any(axis=1)).any())
+
+
+def _verify_record(rec, prev, challenge, device):
+    """one record against the five points before it and the challenge it answers -> (ok, detail)"""
+    from . import pairing, phase2
+    g1, g2 = generators()
+    failed = []
+
+    def ratio(what, a, b, c, d):
+        try:
+            if not pairing.same_ratio(a, b, c, d):
+                failed.append(what)
+        except pairing.PairingError as e:
+            failed.append(f"{what} ({e})")
+    for i, name in enumerate(KEYS):
+        s, sx, spx = rec[f"{name}_g1_s"], rec[f"{name}_g1_sx"], rec[f"{name}_g2_spx"]
+        sp = pok_challenge_point(challenge, i, s, sx, device)
+        ratio(f"{name}: proof of knowledge", s, sx, sp, spx)
+        ratio(f"{name}: link to the points before", prev[f"{name}_g1"], rec[f"{name}_g1"], sp, spx)
+    ratio("tau_g1 / tau_g2", g1, rec["tau_g1"], g2, rec["tau_g2"])
+    ratio("beta_g1 / beta_g2", g1, rec["beta_g1"], g2, rec["beta_g2"])
+    kind = "contribution"
+    if rec["type"] == phase2.TYPE_BEACON:
+        kind = "beacon"
+        if not rec["beacon_hash"] or not rec["num_iterations_exp"] or not 10 <= rec["num_iterations_exp"] <= 63:
+            failed.append("beacon parameters")
+        else:
+            (tau, _, _), _ = key_scalars(phase2.beacon_seed(rec["beacon_hash"], rec["num_iterations_exp"]))
+            if phase2.scale_points(1, prev["tau_g1"], tau, device) != rec["tau_g1"]:
+                failed.append("tau_g1 is not the beacon's tau times the tau_g1 before")
+    who = f"{kind} {rec['name']!r}"
+    return (not failed), (who if not failed else f"{who}: " + "; ".join(failed))
+
+
+def verify(data, device=0, *, urandom=os.urandom):
+    """-> {"ok": bool, "checks": [(name, ok, detail)]} for a .ptau in either state (bytes, or an mmap).  ok of a check: True, False, or
+    None = skipped (does not fail).  urandom supplies the 16-byte scalars of the random linear combinations.  The checks, in order:
+
+      structure       what read_any / read_contributions refuse
+      points          every point of sections 2 - 6 (and 12 - 15) reduced and on its curve (the device's check); none of 2 - 6 infinity
+      subgroup        every point of sections 3, 6, 13 in the subgroup of order r (zkwg_g2_subgroup_device)
+      anchors         point 0 of sections 2 and 3 are the generators
+      powers_2 .. 5   S_a = sum s_i P_i, S_b = sum s_i P_(i+1) have the ratio tau: same_ratio(S_a, S_b, G2, tau G2); section 3:
+                      same_ratio(G1, tau G1, S_a, S_b).  Skipped when a G2 point of the check is outside the subgroup (`subgroup` says so)
+      beta            same_ratio(G1, beta G1, G2, beta G2)
+      record_k        record k: three proofs of knowledge, their links to the points of record k - 1, tau and beta in both groups;
+                      a beacon's tau recomputed
+      last_record     the last record's five points are the file's
+      last_challenge  its next_challenge = BLAKE2b-512(previous challenge | sections 2 - 6); skipped for a truncated file
+      lagrange_12 .. 15   per level q: sum_j s_j Lag_q[j] == sum_k ifft(s)_k P_k, two points compared directly
+    A failure of `structure` or `points` ends the run: nothing after it would mean anything."""
+    from . import pairing
+    checks = []
+
+    def done():
+        return {"ok": all(ok is not False for _, ok, _ in checks), "checks": checks}
+    try:
+        info, state = read_any(data)
+        recs = read_contributions(data)
+    except ValueError as e:
+        checks.append(("structure", False, str(e)))
+        return done()
+    power, sec = info["power"], info["sections"]
+    n = 1 << power
+    checks.append(("structure", True, f"power {power}, ceremony power {info['ceremony_power']}, {state}, " +
+                   (f"{len(recs)} contribution{'s' if len(recs) != 1 else ''}" if recs else "no contributions")))
+    view = memoryview(data)
+    part = lambda sid: view[sec[sid][0]:sec[sid][0] + sec[sid][1]]
+    pt_of = lambda sid: 128 if sid in (3, 6, 13) else 64
+    point = lambda sid, k: bytes(view[sec[sid][0] + k * pt_of(sid):sec[sid][0] + (k + 1) * pt_of(sid)])
+    sids = [2, 3, 4, 5, 6] + ([12, 13, 14, 15] if state == "prepared" else [])
+    # ---- everything the device computes, first: its curve check is the `points` check
+    inf = [sid for sid in (2, 3, 4, 5, 6) if _has_infinity(part(sid), pt_of(sid))]
+    if inf:
+        checks.append(("points", False, f"section {inf[0]} holds a point at infinity"))
+        return done()
+    B = _backend(device)
+    outside, sums, lag = {}, {}, {}
+    sid = 0
+    try:
+        for sid in sids:
+            group, count = (2 if pt_of(sid) == 128 else 1), sec[sid][1] // pt_of(sid)
+            d = B.upload(part(sid))
+            if group == 2:
+                outside[sid] = B.g2_subgroup(d, count)
+            if sid in POWERS and count > 1:
+                sums[sid] = B.rlc(group, d, 0, count - 1, B.upload(urandom(16 * (count - 1))), shifted=True)
+            if sid in LAGRANGE_OF:
+                src = B.upload(part(LAGRANGE_OF[sid]))
+                lag[sid] = []
+                for q in range(power + (2 if sid == 12 else 1)):
+                    m = 1 << q
+                    s = urandom(16 * m)
+                    left = B.rlc(group, d, m - 1, m, B.upload(s))[0]
+                    if q < NTT_MIN_LOG2:
+                        hat = B.upload(b"".join(v.to_bytes(32, "little") for v in ifft_host([int.from_bytes(s[16 * j:16 * j + 16], "little") for j in range(m)], q)))
+                    else:
+                        hat = B.ifft(s, q)
+                    right = B.rlc(group, src, 0, min(m, 2 * n - 1), hat, wide=True)[0]      # (level power + 1: the pad's scalar meets no point)
+                    lag[sid].append(left == right)
+                    del hat
+                del src
+            del d
+    except PtauError as e:
+        if "curve" not in str(e):
+            raise
+        checks.append(("points", False, f"section {sid}: {e}"))
+        return done()
+    checks.append(("points", True, f"sections {', '.join(str(s) for s in sids)}"))
+    bad = {s: v for s, v in outside.items() if v[0]}
+    checks.append(("subgroup", not bad, "; ".join(f"section {s}: {v[0]} point{'s' if v[0] != 1 else ''} outside the subgroup, the first at {v[1]}" for s, v in bad.items())
+                   or f"sections {', '.join(str(s) for s in outside)}"))
+    g1, g2 = generators()
+    checks.append(("anchors", point(2, 0) == g1 and point(3, 0) == g2, "point 0 of sections 2 and 3"))
+    tau_g1, tau_g2 = point(2, 1), point(3, 1)
+
+    def ratio(name, a, b, c, d, detail):
+        try:
+            checks.append((name, pairing.same_ratio(a, b, c, d), detail))
+        except pairing.PairingError as e:
+            if bad and "subgroup" in str(e):             # no pairing is defined there, and `subgroup` has reported why
+                checks.append((name, None, "skipped (a G2 point of the check is outside the subgroup)"))
+            else:
+                checks.append((name, False, str(e)))
+    for s in (2, 3, 4, 5):
+        count = sec[s][1] // pt_of(s)
+        if s == 3:
+            ratio("powers_3", g1, tau_g1, sums[3][0], sums[3][1], f"{count} points")
+        else:
+            ratio(f"powers_{s}", sums[s][0], sums[s][1], g2, tau_g2, f"{count} points")
+    ratio("beta", g1, point(5, 0), g2, point(6, 0), "sections 5 and 6")
+    # ---- the records
+    if recs:
+        prev = {"tau_g1": g1, "tau_g2": g2, "alpha_g1": g1, "beta_g1": g1, "beta_g2": g2}
+        challenge = new_challenge(info["ceremony_power"])
+        for k, rec in enumerate(recs):
+            ok, detail = _verify_record(rec, prev, challenge, device)
+            checks.append((f"record_{k + 1}", ok, detail))
+            prev, before, challenge = rec, challenge, rec["next_challenge"]
+        same = all(rec[name] == point(*RECORD_AT[name]) for name in RECORD_AT)
+        checks.append(("last_record", same, "the last record's five points are the file's" if same else "the last record's five points are not the file's"))
+        if power < info["ceremony_power"]:
+            checks.append(("last_challenge", None, "skipped (truncated)"))
+        else:
+            checks.append(("last_challenge", recs[-1]["next_challenge"] == _points_hash(view, info, before), "the last next_challenge against sections 2 - 6"))
+    for sid in lag:
+        wrong = [q for q, ok in enumerate(lag[sid]) if not ok]
+        checks.append((f"lagrange_{sid}", not wrong, f"level{'s' if len(wrong) != 1 else ''} {', '.join(str(q) for q in wrong)} differ from the powers" if wrong else f"{len(lag[sid])} levels"))
+    return done()
+
+
 def main(argv=None):
-    ap = argparse.ArgumentParser(description="powers of tau: a new file, a contribution or a beacon, the preparation for phase 2, or a description")
+    ap = argparse.ArgumentParser(description="powers of tau: a new file, a contribution or a beacon, the preparation for phase 2, a description, or the verification of a file")
     sub = ap.add_subparsers(dest="cmd", required=True)
     pn = sub.add_parser("new")
     pn.add_argument("power", type=int)
@@ -461,6 +725,9 @@ def main(argv=None):
     pp.add_argument("--device", type=int, default=0)
     pi = sub.add_parser("info")
     pi.add_argument("ptau")
+    pv = sub.add_parser("verify")
+    pv.add_argument("ptau")
+    pv.add_argument("--device", type=int, default=0)
     a = ap.parse_args(argv)
     if a.cmd == "new":
         try:
@@ -469,6 +736,13 @@ def main(argv=None):
             print(f"no file: {e}", file=sys.stderr)
             return 1
         return 0
+    if a.cmd == "verify":
+        with open(a.ptau, "rb") as f, mmap.mmap(f.fileno(), 0, access=mmap.ACCESS_READ) as mm:
+            res = verify(mm, a.device)
+        for name, ok, detail in res["checks"]:
+            print(f"{name}: {'ok' if ok else 'skipped' if ok is None else 'FAILED'}  {detail}")
+        print("the file verifies" if res["ok"] else "the file does NOT verify")
+        return 0 if res["ok"] else 1
     path = a.ptau if a.cmd == "info" else a.ptau_in
     out, why = None, ""
     with open(path, "rb") as f, mmap.mmap(f.fileno(), 0, access=mmap.ACCESS_READ) as mm:
