@@ -641,7 +641,8 @@ void zkwg_zkey_new_stats(double seconds[7], uint64_t ops[8]);
  * command reads circuit_0001.zkey, the key AFTER a contribution): `snarkjs zkey contribute` / `zkey beacon`.  A contribution with
  * secret k sets delta1' = k delta1, delta2' = k delta2, C_i' = k^-1 C_i (section 8), H_j' = k^-1 H_j (section 9); sections 1, 3 - 7 and
  * alpha, beta, gamma are copied.  The record of section 10 (who contributed, the proof of knowledge of k) is the host layer's:
- * zkwg/phase2.py.  Not built: `zkey verify`, the circuit hash, chunked keys.
+ * zkwg/phase2.py, and so is `zkey verify` (zkwg.phase2.verify: zkwg_zkey_new again, then zkwg_point_rlc_device with two arrays and
+ * zkwg_pairing_check, below).  Not built: the circuit hash, chunked keys.
  *
  * zkwg_point_scale_device: d_out[i] = scalar * d_points[i] for n affine points in the zkey's form (64 / 128 bytes, little-endian
  * Montgomery words, zeros = infinity and stay zeros; group 1 / 2; device pointers, 16-byte aligned; d_out may be d_points).  scalar:
@@ -703,7 +704,7 @@ void zkwg_ptau_prepare_stats(double seconds[140], uint64_t ops[8]);
  * scalar.  (`powersoftau new` needs no device: zkwg/ptau.py writes the generators.)  The record of section 7 -- who contributed, the
  * proofs of knowledge, the challenge chain -- is the host layer's (zkwg/ptau.py) and is ZKWG'S OWN: `snarkjs powersoftau verify` does
  * NOT accept the file; `prepare`, `setup` and every reader of the points do -- and `python -m zkwg.ptau verify` checks it (the next
- * block).  Not built: snarkjs-compatible challenge hashes, import / export challenge, `zkey verify`.
+ * block).  Not built: snarkjs-compatible challenge hashes, import / export challenge.
  *
  * zkwg_point_mul_device: d_out[i] = scalars[i] * d_points[i] for n affine points in the zkey's form (64 / 128 bytes, little-endian
  * Montgomery words, zeros = infinity and stay zeros; group 1 / 2; device pointers, 16-byte aligned; d_out may be d_points).
@@ -753,7 +754,8 @@ void zkwg_ptau_apply_key_stats(double seconds[18], uint64_t ops[8]);
  *
  * zkwg_point_rlc_device: out_a = sum_i s_i A_i, out_b = sum_i s_i B_i over n points of one group (1 / 2); s_i: n x 16 bytes on the
  * device, little-endian (any 128-bit value).  d_b may be NULL (one sum; out_b is not written) and may overlap d_a -- d_b = d_a + one
- * point is the shifted form the powers checks need.  Outputs: host memory, the zkey's form, zeros = infinity.  Curve check of every
+ * point is the shifted form the powers checks need; d_b an array of its own (n points under the same scalars) is the form `zkey verify`
+ * folds sections 8 / 9 of a key and of its initial key with.  Outputs: host memory, the zkey's form, zeros = infinity.  Curve check of every
  * point of both arrays first, refusal as above.  piece_points = 0: 2^22; every piece is one multi-exponentiation plan in the classic
  * layout, and the partial sums of the pieces are added on the host.  zkwg_point_rlc32_device: the same with 32-byte scalars, standard
  * form, BELOW r (the plans' rule). */

@@ -1,5 +1,7 @@
 """python -m zkwg.phase2 contribute in.zkey out.zkey --name N [--entropy E]
 python -m zkwg.phase2 beacon in.zkey out.zkey HASHHEX EXP --name N
+python -m zkwg.phase2 verify circuit.r1cs pot.ptau circuit.zkey [--device D]
+python -m zkwg.phase2 verify circuit.zkey --init init.zkey [--device D]
 -- "Phase 2" of the reference's workflow on the device (docs/zk-email-docs/UsageGuide/README.md:149,178-180: `snarkjs zkey contribute` /
 `zkey beacon`; the guide's next command reads circuit_0001.zkey, the key AFTER a contribution, :206).  The key python -m zkwg.setup writes
 has delta = 1: anyone can forge proofs under it.  A contribution with secret k turns delta into k delta (delta1, delta2 times k, the C and
@@ -20,8 +22,16 @@ offline; here it is try-and-increment: x in Fq2 from BLAKE2b(tag | transcript | 
 integers (q = 3 mod 4; Fq2 roots through the norm), then times the twist's cofactor 2 q - r on the device (zkwg_point_scale_device:
 the one scalar here above r).  Nobody knows its discrete logarithm -- a multiple of the generator would let the first contribution be
 forged.  `snarkjs zkey verify` therefore does NOT accept the record (nor the circuit hash, which stays as the file holds it: 64 zero
-bytes after zkwg.setup); every prover and verifier reads the key."""
+bytes after zkwg.setup); every prover and verifier reads the key.
+
+`verify` (`snarkjs zkey verify` / `zkey verifyfrominit`) CHECKS A KEY against its circuit and ceremony file: the initial key is made again
+(zkwg.setup.new_zkey) and everything a contribution must not touch is compared with it byte for byte; delta1 / delta2 are one delta; every
+record's transcript, proof of knowledge and link to the delta1 before it (a beacon's scalar recomputed); and sections 8 and 9 are the
+initial key's divided by that delta -- each folded, together with the initial key's, into one point per key by a random linear
+combination on the device (zkwg.ptau.rlc, the two-array form of zkwg_point_rlc_device) and compared under delta2 by ONE pairing check on
+the host (zkwg.pairing).  See `verify_from_init` below for the checks.  The records are zkwg's, so this is the command that reads them."""
 import argparse
+import contextlib
 import ctypes as C
 import hashlib
 import mmap
@@ -294,8 +304,188 @@ def beacon(zkey_bytes, name, beacon_hash, num_iterations_exp, device=0):
     return _contribute(zkey_bytes, k, s, {"name": name, "type": TYPE_BEACON, "num_iterations_exp": num_iterations_exp, "beacon_hash": bh}, device)
 
 
+# ---- verify ---------------------------------------------------------------------------------------------------------------------------------------
+HEADER_POINTS = (("alpha1", 64), ("beta1", 64), ("beta2", 128), ("gamma2", 128), ("delta1", 64), ("delta2", 128))      # after the 84 bytes of section 2
+SECTION_ENTRY = {3: 64, 5: 64, 6: 64, 7: 128}     # bytes per point of the sections a contribution copies (section 4: a u32 count, 44 bytes a coefficient)
+FOLD_PIECE = 0                                    # points per multi-exponentiation plan of a fold (0: zkwg_point_rlc_device's own 2^22)
+
+
+def _first_difference(a, b):
+    """the lowest index at which two buffers of one length differ, or None"""
+    import numpy as np
+    x, y = np.frombuffer(a, dtype=np.uint8), np.frombuffer(b, dtype=np.uint8)
+    for at in range(0, len(x), 1 << 24):
+        d = np.flatnonzero(x[at:at + (1 << 24)] != y[at:at + (1 << 24)])
+        if len(d):
+            return at + int(d[0])
+
+
+def _zkey_check(data):
+    """zkwg_zkey_check (host only): the header, every section's size against it, the coefficients of section 4"""
+    import numpy as np
+    lib = _lib.load()
+    a = np.frombuffer(data, dtype=np.uint8)            # (no copy; works for an mmap)
+    try:
+        rc = lib.zkwg_zkey_check(a.ctypes.data, a.size, None, None, None)
+    finally:
+        del a
+    if rc != 0:
+        _fail(lib, rc)
+
+
+def _verify_record(rec, circuit_hash, earlier, before, device):
+    """one record against the circuit hash, the records before it and the delta1 before it -> (ok, detail)"""
+    from . import pairing
+    failed = []
+
+    def ratio(what, a, b, c, d):
+        try:
+            if not pairing.same_ratio(a, b, c, d):
+                failed.append(what)
+        except pairing.PairingError as e:
+            failed.append(f"{what} ({e})")
+    transcript = hashlib.blake2b(circuit_hash + b"".join(r["raw"] for r in earlier) + rec["g1_s"] + rec["g1_sx"], digest_size=64).digest()
+    if transcript != rec["transcript"]:
+        failed.append("transcript")
+    sp = challenge_g2(rec["transcript"], device)      # (of the STORED transcript: a wrong one has failed above, and the ratios still say what else holds)
+    ratio("proof of knowledge", rec["g1_s"], rec["g1_sx"], sp, rec["g2_spx"])
+    ratio("link to the delta1 before", before, rec["delta_after"], sp, rec["g2_spx"])
+    kind = "contribution"
+    if rec["type"] == TYPE_BEACON:
+        kind = "beacon"
+        if not rec["beacon_hash"] or not rec["num_iterations_exp"] or not 10 <= rec["num_iterations_exp"] <= 63:
+            failed.append("beacon parameters")
+        else:
+            k, _ = contribution_scalars(beacon_seed(rec["beacon_hash"], rec["num_iterations_exp"]))
+            if scale_points(1, before, k, device) != rec["delta_after"]:
+                failed.append("delta_after is not the beacon's scalar times the delta1 before")
+    who = f"{kind} {rec['name']!r}"
+    return (not failed), (who if not failed else f"{who}: " + "; ".join(failed))
+
+
+def verify_from_init(init_zkey_bytes, zkey_bytes, device=0, *, urandom=os.urandom):
+    """-> {"ok": bool, "checks": [(name, ok, detail)]} for a key against the INITIAL key of its circuit (both bytes, or an mmap).  ok of a
+    check: True, False, or None = skipped (does not fail).  urandom supplies the 16-byte scalars of the folds.  The checks, in order:
+
+      structure       zkwg_zkey_check accepts both files, section 10 parses, nVars, nPublic, the domain and the sizes of sections 1 - 9 are
+                      the initial key's
+      header          alpha1, beta1, beta2, gamma2 and the 64 bytes of the circuit hash are the initial key's
+      section_3 .. 7  byte-equal to the initial key's; the detail names the first entry that differs
+      delta           delta1 is not infinity and same_ratio(G1, delta1, G2, delta2); a delta2 the pairing refuses fails here
+      record_k        record k: its transcript recomputed; g2_sp = challenge_g2(transcript), same_ratio(g1_s, g1_sx, g2_sp, g2_spx) and
+                      same_ratio(delta1 before, delta_after, g2_sp, g2_spx); a beacon's scalar recomputed and applied
+      last_record     the last record's delta_after is the key's delta1; without records delta1, delta2 are the initial key's
+      section_8, 9    S' = sum s_i P'_i over the key and S = sum s_i P_i over the initial key, random 16-byte s_i, from ONE two-array fold
+                      (zkwg.ptau.rlc's `other`); the key's points are the initial ones divided by delta, so e(S', delta2') = e(S, delta2):
+                      pairing.same_ratio(S', S, delta2 of the initial key, delta2 of the key) -- its arguments (a, b, c, d) mean
+                      e(a, d) = e(b, c).  A point off its curve is the device's refusal and fails the check
+    A failure of `structure` ends the run.  An initial key that holds records itself (the key before this contribution, for a coordinator
+    who checks one contribution at a time) is trusted as it is: the key must repeat its records, and the first new one links to its delta1."""
+    from . import pairing, ptau
+    checks = []
+
+    def done():
+        return {"ok": all(ok is not False for _, ok, _ in checks), "checks": checks}
+    init, key = init_zkey_bytes, zkey_bytes
+    try:
+        walked = []
+        for name, data in (("the initial key", init), ("the key", key)):
+            try:
+                s = zkey.sections(data)
+                missing = [sid for sid in range(1, 10) if sid not in s]
+                if missing or s[2][1] != 84 + sum(size for _, size in HEADER_POINTS):
+                    raise Phase2Error(f"section {missing[0]} is missing" if missing else "section 2 is not a groth16 header")
+                _zkey_check(data)
+                walked.append((s,) + read_contributions(data))
+            except ValueError as e:                    # (Phase2Error, and what the section walk of zkwg.zkey raises)
+                raise Phase2Error(f"{name}: {e}")
+        (sec0, hash0, recs0), (sec, circuit_hash, recs) = walked
+        shape0, shape = (struct.unpack_from("<III", d, s[2][0] + 72) for d, s in ((init, sec0), (key, sec)))
+        if shape != shape0:
+            raise Phase2Error(f"nVars, nPublic, domain are {shape}, the initial key's {shape0}")
+        for sid in range(1, 10):
+            if sec[sid][1] != sec0[sid][1]:
+                raise Phase2Error(f"section {sid} holds {sec[sid][1]} bytes, the initial key's {sec0[sid][1]}")
+    except Phase2Error as e:
+        checks.append(("structure", False, str(e)))
+        return done()
+    checks.append(("structure", True, f"{shape[0]} wires, {shape[1]} public, domain {shape[2]}, " +
+                   (f"{len(recs)} contribution{'s' if len(recs) != 1 else ''}" if recs else "no contributions")))
+    view0, view = memoryview(init), memoryview(key)
+    part0 = lambda sid: view0[sec0[sid][0]:sec0[sid][0] + sec0[sid][1]]
+    part = lambda sid: view[sec[sid][0]:sec[sid][0] + sec[sid][1]]
+    hdr0, hdr, at = {}, {}, 84
+    for name, size in HEADER_POINTS:
+        hdr0[name], hdr[name] = bytes(part0(2)[at:at + size]), bytes(part(2)[at:at + size])
+        at += size
+    differ = [name for name in ("alpha1", "beta1", "beta2", "gamma2") if hdr[name] != hdr0[name]] + (["the circuit hash"] if circuit_hash != hash0 else [])
+    checks.append(("header", not differ, f"{', '.join(differ)} differ{'s' if len(differ) == 1 else ''} from the initial key's" if differ else "alpha1, beta1, beta2, gamma2, the circuit hash"))
+    for sid in (3, 4, 5, 6, 7):
+        d = _first_difference(part(sid), part0(sid))
+        if d is None:
+            checks.append((f"section_{sid}", True, f"{sec[sid][1]} bytes"))
+        elif sid == 4:
+            checks.append(("section_4", False, "the count differs" if d < 4 else f"coefficient {(d - 4) // 44} differs (byte {d} of the section)"))
+        else:
+            checks.append((f"section_{sid}", False, f"point {d // SECTION_ENTRY[sid]} differs"))
+    g1, g2 = ptau.generators()
+
+    def ratio(name, a, b, c, d, detail):
+        try:
+            checks.append((name, pairing.same_ratio(a, b, c, d), detail))
+        except pairing.PairingError as e:
+            checks.append((name, False, str(e)))
+    if not any(hdr["delta1"]):
+        checks.append(("delta", False, "delta1 is the point at infinity"))
+    else:
+        ratio("delta", g1, hdr["delta1"], g2, hdr["delta2"], "delta1 and delta2 are one delta")
+    # ---- the records
+    before = hdr0["delta1"]
+    for k, rec in enumerate(recs):
+        if k < len(recs0):
+            same = rec["raw"] == recs0[k]["raw"]
+            checks.append((f"record_{k + 1}", same, "as in the initial key" if same else "differs from the initial key's record"))
+            continue
+        ok, detail = _verify_record(rec, circuit_hash, recs[:k], before, device)
+        checks.append((f"record_{k + 1}", ok, detail))
+        before = rec["delta_after"]
+    if len(recs) < len(recs0):
+        checks.append(("last_record", False, f"the key holds {len(recs)} records, the initial key {len(recs0)}"))
+    elif len(recs) > len(recs0):
+        same = recs[-1]["delta_after"] == hdr["delta1"]
+        checks.append(("last_record", same, "the last record's delta_after is the key's delta1" if same else "the last record's delta_after is not the key's delta1"))
+    else:
+        same = hdr["delta1"] == hdr0["delta1"] and hdr["delta2"] == hdr0["delta2"]
+        checks.append(("last_record", same, "no contribution: delta is the initial key's" if same else "no contribution, but delta is not the initial key's"))
+    # ---- sections 8 and 9: one fold of both keys, one pairing check
+    B = ptau._backend(device)
+    for sid in (8, 9):
+        name, n = f"section_{sid}", sec[sid][1] // 64
+        if n == 0:
+            checks.append((name, True, "no points"))
+            continue
+        try:
+            s_key, s_init = B.rlc(1, B.upload(part(sid)), 0, n, B.upload(urandom(16 * n)), piece=FOLD_PIECE, other=B.upload(part0(sid)))
+        except ptau.PointRefused as e:                 # (the device's curve check, by its return code)
+            checks.append((name, False, str(e)))
+            continue
+        if not any(s_key) or not any(s_init):          # (every point at infinity on both sides is a key without such wires; on one side only, a difference)
+            both = not any(s_key) and not any(s_init)
+            checks.append((name, both, f"{n} points, all at infinity" if both else "one fold is the point at infinity, the other is not"))
+        else:
+            ratio(name, s_key, s_init, hdr0["delta2"], hdr["delta2"], f"{n} points")
+    return done()
+
+
+def verify(r1cs_bytes, ptau_bytes, zkey_bytes, device=0, *, urandom=os.urandom):
+    """`snarkjs zkey verify`: the initial key is made again from the circuit and the PREPARED powers of tau (zkwg.setup.new_zkey, which
+    raises what it refuses there), the rest is verify_from_init.  -> {"ok": bool, "checks": [(name, ok, detail)]}"""
+    from . import setup
+    return verify_from_init(setup.new_zkey(r1cs_bytes, ptau_bytes, device), zkey_bytes, device, urandom=urandom)
+
+
 def main(argv=None):
-    ap = argparse.ArgumentParser(description="phase 2 of the groth16 set-up: a contribution or a beacon on a .zkey")
+    ap = argparse.ArgumentParser(description="phase 2 of the groth16 set-up: a contribution or a beacon on a .zkey, or the verification of a key")
     sub = ap.add_subparsers(dest="cmd", required=True)
     pc = sub.add_parser("contribute")
     pb = sub.add_parser("beacon")
@@ -308,7 +498,14 @@ def main(argv=None):
     for p in (pc, pb):
         p.add_argument("--name", required=True)
         p.add_argument("--device", type=int, default=0)
+    pv = sub.add_parser("verify", description="circuit.r1cs pot.ptau circuit.zkey: the initial key is made again from the circuit and the prepared "
+                        "powers of tau; circuit.zkey --init init.zkey: it is read from a file (a coordinator makes it once)")
+    pv.add_argument("files", nargs="+", metavar="FILE", help="circuit.r1cs pot.ptau circuit.zkey, or with --init: circuit.zkey")
+    pv.add_argument("--init", metavar="INIT_ZKEY")
+    pv.add_argument("--device", type=int, default=0)
     a = ap.parse_args(argv)
+    if a.cmd == "verify":
+        return _main_verify(a, pv)
     z, why = None, ""
     with open(a.zkey_in, "rb") as f, mmap.mmap(f.fileno(), 0, access=mmap.ACCESS_READ) as mm:
         try:
@@ -320,6 +517,33 @@ def main(argv=None):
         return 1
     open(a.zkey_out, "wb").write(z)
     return 0
+
+
+def _main_verify(a, parser):
+    if len(a.files) != (1 if a.init else 3):
+        parser.error("verify takes circuit.r1cs pot.ptau circuit.zkey, or circuit.zkey --init init.zkey")
+    res, why = None, ""
+    try:
+        with contextlib.ExitStack() as stack:
+            def mapped(path):                          # (an empty file cannot be mapped: ValueError)
+                f = stack.enter_context(open(path, "rb"))
+                return stack.enter_context(mmap.mmap(f.fileno(), 0, access=mmap.ACCESS_READ))
+            key = mapped(a.files[-1])
+            if a.init:
+                res = verify_from_init(mapped(a.init), key, a.device)
+            else:
+                with open(a.files[0], "rb") as f:
+                    r1cs = f.read()
+                res = verify(r1cs, mapped(a.files[1]), key, a.device)
+    except (ValueError, OSError) as e:                 # (a file that is missing or empty, and what the set-up refuses in the .r1cs or the .ptau)
+        why = str(e)
+    if res is None:
+        print(f"no verdict: {why}", file=sys.stderr)
+        return 1
+    for name, ok, detail in res["checks"]:
+        print(f"{name}: {'ok' if ok else 'skipped' if ok is None else 'FAILED'}  {detail}")
+    print("the key verifies" if res["ok"] else "the key does NOT verify")
+    return 0 if res["ok"] else 1
 
 
 if __name__ == "__main__":

@@ -45,8 +45,8 @@ offline), so `snarkjs powersoftau verify` does NOT accept the file; `prepare`, `
 of sections 3, 6, 13 in the subgroup of order r (zkwg_g2_subgroup_device), the sections powers of ONE tau (and alpha, beta times them),
 every record's proofs of knowledge and its link to the record before, the challenge chain's last link, and the Lagrange sections against
 the powers.  A section of 2^21 points becomes the four points of one pairing check by a random linear combination on the device
-(zkwg_point_rlc_device); the pairings themselves, a few dozen, run on the host (zkwg.pairing).  See `verify` below for the checks.
-Not built: snarkjs-compatible challenge hashes, import / export challenge, `zkey verify`."""
+(zkwg_point_rlc_device); the pairings themselves, a few dozen, run on the host (zkwg.pairing).  See `verify` below for the checks.  (`zkey verify`, the check of a phase-2 key, is zkwg.phase2.verify; it folds
+with `rlc`'s two-array form.)  Not built: snarkjs-compatible challenge hashes, import / export challenge."""
 import argparse
 import ctypes as C
 import hashlib
@@ -65,6 +65,11 @@ LAGRANGE = {12: "tau_g1", 13: "tau_g2", 14: "alpha_tau_g1", 15: "beta_tau_g1"}
 
 class PtauError(ValueError):
     pass
+
+
+class PointRefused(PtauError):
+    """zkwg_point_rlc_device refused its points: ZKWG_RC_BAD_CONFIG, which that call returns for one reason only -- a point of either
+    array is not reduced or not on its curve"""
 
 
 def read_ptau(data, prepared=True):
@@ -209,8 +214,11 @@ def new(power):
     return write_ptau(power, {2: g1 * (2 * n - 1), 3: g2 * n, 4: g1 * n, 5: g1 * n, 6: g2})
 
 
+BAD_CONFIG = -1                                   # ZKWG_RC_BAD_CONFIG: the one code zkwg_last_error has a message for
+
+
 def _fail(lib, rc):
-    msg = lib.zkwg_last_error().decode() if rc == -1 else ""
+    msg = lib.zkwg_last_error().decode() if rc == BAD_CONFIG else ""
     raise PtauError(f"{lib.zkwg_strerror(rc).decode()}{': ' + msg if msg else ''}")
 
 
@@ -471,17 +479,21 @@ class _Device:
             _fail(self.lib, rc)
         return n_bad.value, (first.value if n_bad.value else None)
 
-    def rlc(self, group, points, first, n, scalars, wide=False, shifted=False, piece=0):
-        """sum_i s_i P[first + i], i < n -> (sum, None); shifted: also sum_i s_i P[first + i + 1] from the same upload.  scalars: n x 16
-        bytes on the device (wide: n x 32, below r)"""
+    def rlc(self, group, points, first, n, scalars, wide=False, shifted=False, piece=0, other=None):
+        """sum_i s_i P[first + i], i < n -> (sum, None); shifted: also sum_i s_i P[first + i + 1] from the same upload; other (a second
+        array of the same group on the device): also sum_i s_i other[first + i], from the same call.  scalars: n x 16 bytes on the device
+        (wide: n x 32, below r)"""
         pt = 64 if group == 1 else 128
         a = points.data_ptr() + first * pt
+        b = a + pt if shifted else other.data_ptr() + first * pt if other is not None else None
         out_a, out_b = (C.c_uint8 * pt)(), (C.c_uint8 * pt)()
         fn = self.lib.zkwg_point_rlc32_device if wide else self.lib.zkwg_point_rlc_device
-        rc = fn(self.device, group, a, a + pt if shifted else None, n, scalars.data_ptr(), piece, out_a, out_b if shifted else None, 0)
+        rc = fn(self.device, group, a, b, n, scalars.data_ptr(), piece, out_a, out_b if b is not None else None, 0)
+        if rc == BAD_CONFIG:
+            raise PointRefused(f"{self.lib.zkwg_strerror(rc).decode()}: {self.lib.zkwg_last_error().decode()}")
         if rc != 0:
             _fail(self.lib, rc)
-        return bytes(out_a), (bytes(out_b) if shifted else None)
+        return bytes(out_a), (bytes(out_b) if b is not None else None)
 
     def ifft(self, scalars16, q):
         """2^q 16-byte values (bytes) -> their inverse field transform over the 2^q-th roots, 32-byte values on the device"""
@@ -514,14 +526,20 @@ def g2_subgroup(points, device=0):
     return B.g2_subgroup(B.upload(points), len(points) // 128) if points else (0, None)
 
 
-def rlc(group, points, scalars, shifted=False, wide=False, piece=0, device=0):
+def rlc(group, points, scalars, shifted=False, wide=False, piece=0, device=0, other=None):
     """sum_i s_i P_i for points and 16-byte scalars as bytes (wide: 32-byte scalars below r) -> the point in the zkey's form
-    (zkwg_point_rlc_device).  shifted: one point more than scalars; -> (sum_i s_i P_i, sum_i s_i P_(i+1)) from ONE array on the device"""
+    (zkwg_point_rlc_device).  shifted: one point more than scalars; -> (sum_i s_i P_i, sum_i s_i P_(i+1)) from ONE array on the device.
+    other: as many points of the same group in an array of their own; -> (sum_i s_i P_i, sum_i s_i other_i) from ONE call, the two
+    arrays under the same scalars (what zkwg.phase2.verify folds sections 8 / 9 of two keys with)"""
     pt, sb = (64 if group == 1 else 128), (32 if wide else 16)
     n = len(scalars) // sb
     if len(scalars) != n * sb or len(points) != (n + (1 if shifted else 0)) * pt or n == 0:
         raise PtauError("one scalar per whole point (and one point more in the shifted form)")
+    if other is not None and (shifted or len(other) != len(points)):
+        raise PtauError("the other array holds as many points of the same group, and there is no shifted form of two arrays")
     B = _backend(device)
+    if other is not None:
+        return B.rlc(group, B.upload(points), 0, n, B.upload(scalars), wide=wide, piece=piece, other=B.upload(other))
     out = B.rlc(group, B.upload(points), 0, n, B.upload(scalars), wide=wide, shifted=shifted, piece=piece)
     return out if shifted else out[0]
 
