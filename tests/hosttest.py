@@ -2,15 +2,10 @@
 core (tests/native/hosttest.cpp), and a Python restatement of zk_expand's segment semantics
 so that CPU tests can turn a compact image into a witness without a GPU."""
 import ctypes as C
-import os
-import subprocess
 
-from conftest import ROOT
+import nativelib
 
 P = 21888242871839275222246405745257275088548364400416034343698204186575808495617
-_SO = os.path.join(ROOT, "tests", "native", "libzkwg_hosttest.so")
-_SRC = os.path.join(ROOT, "tests", "native", "hosttest.cpp")
-_CSRC = os.path.join(ROOT, "zk-email-verify_amd", "csrc")
 
 
 class Seg(C.Structure):
@@ -19,16 +14,9 @@ class Seg(C.Structure):
                 ("r0", C.c_uint32), ("pad", C.c_uint32)]
 
 
-_WSO = os.path.join(ROOT, "tests", "native", "libzkwg_wavetest.so")
-
-
 def load_wave():
     """tests/native/wavetest.cpp: csrc/zkwg_rsa_wave.h -- the RSA path the device runs -- on a 64-fiber wavefront (wavesim.h)"""
-    src = [os.path.join(ROOT, "tests", "native", f) for f in ("wavetest.cpp", "wavesim.h")]
-    deps = src + [os.path.join(_CSRC, f) for f in os.listdir(_CSRC) if f.endswith(".h")]
-    if not os.path.exists(_WSO) or any(os.path.getmtime(d) > os.path.getmtime(_WSO) for d in deps):
-        subprocess.check_call(["g++", "-O2", "-std=c++17", "-shared", "-fPIC", "-I", _CSRC, "-I", os.path.join(ROOT, "tests", "native"), src[0], "-o", _WSO])
-    lib = C.CDLL(_WSO)
+    lib = nativelib.build("wavetest", extra_includes=(nativelib.NATIVE,))
     lib.wt_run_rsa.restype = C.c_int
     lib.wt_run_rsa.argtypes = [C.c_void_p] * 6 + [C.POINTER(C.c_uint64)]
     lib.wt_run_rslb_merge.restype = C.c_int
@@ -37,10 +25,7 @@ def load_wave():
 
 
 def load():
-    deps = [_SRC] + [os.path.join(_CSRC, f) for f in os.listdir(_CSRC) if f.endswith(".h")]
-    if not os.path.exists(_SO) or any(os.path.getmtime(d) > os.path.getmtime(_SO) for d in deps):
-        subprocess.check_call(["g++", "-O2", "-std=c++17", "-shared", "-fPIC", "-I", _CSRC, _SRC, "-o", _SO])
-    lib = C.CDLL(_SO)
+    lib = nativelib.build("hosttest")
     lib.ht_create.restype = C.c_void_p
     lib.ht_create.argtypes = [C.c_void_p]
     lib.ht_create_sym.restype = C.c_void_p

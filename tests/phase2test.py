@@ -1,25 +1,12 @@
 """Test-only helpers of phase 2: the host build of csrc/zkwg_phase2_core.h (tests/native/phase2test.cpp) -- the recoder, the scaling
 series of the kernels on the CPU and the file operation over it."""
 import ctypes as C
-import os
-import subprocess
 
-from conftest import ROOT
-
-_SO = os.path.join(ROOT, "tests", "native", "libzkwg_phase2test.so")
-_SRC = os.path.join(ROOT, "tests", "native", "phase2test.cpp")
-_CSRC = os.path.join(ROOT, "zk-email-verify_amd", "csrc")
-_lib = None
+import nativelib
 
 
 def load():
-    global _lib
-    if _lib is not None:
-        return _lib
-    deps = [_SRC, os.path.join(ROOT, "include", "zkwg.h")] + [os.path.join(_CSRC, f) for f in os.listdir(_CSRC) if f.endswith(".h")]
-    if not os.path.exists(_SO) or any(os.path.getmtime(d) > os.path.getmtime(_SO) for d in deps):
-        subprocess.check_call(["g++", "-O2", "-std=c++17", "-shared", "-fPIC", "-I", _CSRC, _SRC, "-o", _SO])
-    lib = C.CDLL(_SO)
+    lib = nativelib.build("phase2test")
     u64p = C.POINTER(C.c_uint64)
     lib.p2_violations.restype = C.c_ulonglong
     lib.p2_recode.restype = None
@@ -30,7 +17,6 @@ def load():
     lib.p2_apply_size.argtypes = [C.c_char_p, C.c_uint64, C.c_uint64, u64p, C.c_char_p, C.c_uint64]
     lib.p2_apply.restype = C.c_int
     lib.p2_apply.argtypes = [C.c_char_p, C.c_uint64, C.c_char_p, C.c_char_p, C.c_uint64, C.c_void_p, C.c_uint64, u64p, C.c_char_p, C.c_uint64]
-    _lib = lib
     return lib
 
 

@@ -1,28 +1,16 @@
 """Test-only helpers of a powers-of-tau contribution: the host build of csrc/zkwg_ptau_key_core.h (tests/native/ptaukeytest.cpp) -- the
 regular recoding, the per-lane scalars c t^k, "each point times its own scalar" on the CPU and the file operation over it."""
 import ctypes as C
-import os
-import subprocess
 
-from conftest import ROOT
+import nativelib
 
 R = 21888242871839275222246405745257275088548364400416034343698204186575808495617
-_SO = os.path.join(ROOT, "tests", "native", "libzkwg_ptaukeytest.so")
-_SRC = os.path.join(ROOT, "tests", "native", "ptaukeytest.cpp")
-_CSRC = os.path.join(ROOT, "zk-email-verify_amd", "csrc")
-_lib = None
 # the scalars every multiplication test meets: the ends of the range, both parities there, the only two that meet P = +-Q (0, r - 1)
 EDGES = [0, 1, 2, 3, 4, R - 2, R - 1, 1 << 253, R - 3]
 
 
 def load():
-    global _lib
-    if _lib is not None:
-        return _lib
-    deps = [_SRC, os.path.join(ROOT, "include", "zkwg.h")] + [os.path.join(_CSRC, f) for f in os.listdir(_CSRC) if f.endswith(".h")]
-    if not os.path.exists(_SO) or any(os.path.getmtime(d) > os.path.getmtime(_SO) for d in deps):
-        subprocess.check_call(["g++", "-O2", "-std=c++17", "-shared", "-fPIC", "-I", _CSRC, _SRC, "-o", _SO])
-    lib = C.CDLL(_SO)
+    lib = nativelib.build("ptaukeytest")
     u64, u64p = C.c_uint64, C.POINTER(C.c_uint64)
     lib.pk_violations.restype = C.c_ulonglong
     lib.pk_window.restype = C.c_uint32
@@ -36,7 +24,6 @@ def load():
     lib.pk_apply_key_size.argtypes = [C.c_char_p, u64, u64, u64p, C.c_char_p, u64]
     lib.pk_apply_key.restype = C.c_int
     lib.pk_apply_key.argtypes = [C.c_char_p, u64, C.c_char_p, C.c_char_p, C.c_char_p, C.c_char_p, u64, C.c_void_p, u64, u64p, u64, C.c_char_p, u64]
-    _lib = lib
     return lib
 
 

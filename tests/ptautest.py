@@ -1,26 +1,14 @@
 """Test-only helpers of the powers-of-tau preparation: the host build of csrc/zkwg_ptau_core.h (tests/native/ptautest.cpp) -- the twiddle
 recoder, the transform over points on the CPU and the file operation over it -- and an unprepared toy ceremony from a known trapdoor."""
 import ctypes as C
-import os
-import subprocess
 
-from conftest import ROOT
+import nativelib
 
 R = 21888242871839275222246405745257275088548364400416034343698204186575808495617
-_SO = os.path.join(ROOT, "tests", "native", "libzkwg_ptautest.so")
-_SRC = os.path.join(ROOT, "tests", "native", "ptautest.cpp")
-_CSRC = os.path.join(ROOT, "zk-email-verify_amd", "csrc")
-_lib = None
 
 
 def load():
-    global _lib
-    if _lib is not None:
-        return _lib
-    deps = [_SRC, os.path.join(ROOT, "include", "zkwg.h")] + [os.path.join(_CSRC, f) for f in os.listdir(_CSRC) if f.endswith(".h")]
-    if not os.path.exists(_SO) or any(os.path.getmtime(d) > os.path.getmtime(_SO) for d in deps):
-        subprocess.check_call(["g++", "-O2", "-std=c++17", "-shared", "-fPIC", "-I", _CSRC, _SRC, "-o", _SO])
-    lib = C.CDLL(_SO)
+    lib = nativelib.build("ptautest")
     u64p = C.POINTER(C.c_uint64)
     lib.pt_violations.restype = C.c_ulonglong
     lib.pt_table.restype = None
@@ -31,7 +19,6 @@ def load():
     lib.pt_prepare_size.argtypes = [C.c_char_p, C.c_uint64, C.c_uint32, u64p, C.c_char_p, C.c_uint64]
     lib.pt_prepare.restype = C.c_int
     lib.pt_prepare.argtypes = [C.c_char_p, C.c_uint64, C.c_uint32, C.c_void_p, C.c_uint64, u64p, C.c_char_p, C.c_uint64]
-    _lib = lib
     return lib
 
 

@@ -2,29 +2,17 @@
 system with every class of coefficient in all three matrices, a toy powers-of-tau ceremony from a known (tau, alpha, beta), and the key
 oracle/pyref/groth16.py makes from the same trapdoor with gamma = delta = 1 -- which a set-up from those powers must equal byte for byte."""
 import ctypes as C
-import os
 import random
-import subprocess
 
-from conftest import ROOT
+import nativelib
 
 R = 21888242871839275222246405745257275088548364400416034343698204186575808495617
 Q = 21888242871839275222246405745257275088696311157297823662689037894645226208583
-_SO = os.path.join(ROOT, "tests", "native", "libzkwg_setuptest.so")
-_SRC = os.path.join(ROOT, "tests", "native", "setuptest.cpp")
-_CSRC = os.path.join(ROOT, "zk-email-verify_amd", "csrc")
-_lib = None
 
 
 def load():
-    global _lib
-    if _lib is not None:
-        return _lib
     from zkwg._lib import SetupSlices
-    deps = [_SRC, os.path.join(ROOT, "include", "zkwg.h")] + [os.path.join(_CSRC, f) for f in os.listdir(_CSRC) if f.endswith(".h")]
-    if not os.path.exists(_SO) or any(os.path.getmtime(d) > os.path.getmtime(_SO) for d in deps):
-        subprocess.check_call(["g++", "-O2", "-std=c++17", "-shared", "-fPIC", "-I", _CSRC, _SRC, "-o", _SO])
-    lib = C.CDLL(_SO)
+    lib = nativelib.build("setuptest")
     u64p = C.POINTER(C.c_uint64)
     lib.st_violations.restype = C.c_ulonglong
     lib.st_ptau_parse.restype = C.c_int
@@ -37,7 +25,6 @@ def load():
     lib.st_fixed_base.argtypes = [C.c_int, C.c_char_p, C.c_uint64, C.c_void_p]
     lib.st_long_threshold.restype = C.c_uint
     lib.st_chunk.restype = C.c_uint
-    _lib = lib
     return lib
 
 

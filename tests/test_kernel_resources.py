@@ -2,59 +2,22 @@
 no scratch memory in any kernel of zkwg_kernels_expand3.hip -- a struct passed by reference to an out-of-line function once
 cost the Montgomery kernels 1.39 x their algorithmic HBM writes -- and the register budgets that give
 the standard-form kernels 8 wavefronts per SIMD."""
-import os
-import re
-import shutil
-import subprocess
-
-import pytest
-
-from conftest import ROOT
-
-CSRC = os.path.join(ROOT, "zk-email-verify_amd", "csrc")
-
+import kernel_resources
 
 _SOURCES = ("zkwg_kernels_rslb.hip", "zkwg_kernels_expand3.hip", "zkwg_kernels_msm.hip", "zkwg_kernels_ntt.hip")
-_compiles = {}
 
 
-def _start_compiles(tmpdir):
-    """the four cross-compilations of this module run side by side (each is one hipcc process of 30-60 s)"""
-    hipcc = shutil.which("hipcc") or "/opt/rocm/bin/hipcc"
-    for src in _SOURCES:
-        if src not in _compiles:
-            err = open(os.path.join(tmpdir, src + ".err"), "w+")
-            _compiles[src] = (subprocess.Popen([hipcc, "-O3", "-std=c++17", "--offload-arch=gfx950", "-c", os.path.join(CSRC, src), "-o",
-                                                os.path.join(tmpdir, src + ".o"), "-Rpass-analysis=kernel-resource-usage"], stdout=subprocess.DEVNULL, stderr=err), err)
+def _resource_usage(src):
+    kernel_resources.start(*_SOURCES)       # the four cross-compilations of this module run side by side
+    return kernel_resources.usage(src)
 
 
-def _resource_usage(src, obj):
-    import tempfile
-    if src not in _compiles:
-        _start_compiles(tempfile.mkdtemp(prefix="zkwg_res_"))
-    proc, err = _compiles[src]
-    assert proc.wait(timeout=900) == 0
-    err.seek(0)
-    stderr = err.read()
-    info, cur = {}, None
-    for line in stderr.splitlines():
-        m = re.search(r"Function Name: (\S+)", line)
-        if m:
-            cur = m.group(1)
-            info[cur] = {}
-            continue
-        m = re.search(r"remark:\s+([A-Za-z ]+?)(?: \[[^\]]*\])?: (\d+)", line)
-        if m and cur:
-            info[cur][m.group(1).strip()] = int(m.group(2))
-    return info
-
-
-@pytest.mark.skipif(not (shutil.which("hipcc") or os.path.exists("/opt/rocm/bin/hipcc")), reason="hipcc not available")
-def test_soft_line_break_chunk_hashes_use_no_scratch_memory(tmp_path):
+@kernel_resources.needs_hipcc
+def test_soft_line_break_chunk_hashes_use_no_scratch_memory():
     # zk_rslb_chunks (one Poseidon(16) per lane, 786 k per batch): the dense mixes hold the old state in registers (153 VGPRs) and
     # fetch their 153 table limbs 9 at a time; if the compiler hoists those scalar loads, or does not unroll the 17
     # multiply-accumulates of an output, the state lands in scratch (624 B .. 6 KB per lane were seen on the way)
-    info = _resource_usage("zkwg_kernels_rslb.hip", tmp_path / "rslb.o")
+    info = _resource_usage("zkwg_kernels_rslb.hip")
     ks = [v for name, v in info.items() if "zk_rslb_chunks" in name]
     assert len(ks) == 8, sorted(info)               # the evaluator's variants (ZKWG_RSLB_V)
     for k in ks:
@@ -69,9 +32,9 @@ def test_soft_line_break_chunk_hashes_use_no_scratch_memory(tmp_path):
         assert next(v for name, v in info.items() if frag in name).get("ScratchSize") == 0, frag
 
 
-@pytest.mark.skipif(not (shutil.which("hipcc") or os.path.exists("/opt/rocm/bin/hipcc")), reason="hipcc not available")
-def test_streaming_kernels_use_no_scratch_memory_and_keep_their_occupancy(tmp_path):
-    info = _resource_usage("zkwg_kernels_expand3.hip", tmp_path / "x3.o")
+@kernel_resources.needs_hipcc
+def test_streaming_kernels_use_no_scratch_memory_and_keep_their_occupancy():
+    info = _resource_usage("zkwg_kernels_expand3.hip")
     kernels = {k: v for k, v in info.items() if "zk_" in k}
     assert len(kernels) >= 20, sorted(info)
     for k, v in kernels.items():
@@ -85,14 +48,14 @@ def test_streaming_kernels_use_no_scratch_memory_and_keep_their_occupancy(tmp_pa
     assert by("13zk_o0_rows_fr")["Occupancy"] >= 4, by("13zk_o0_rows_fr")
 
 
-@pytest.mark.skipif(not (shutil.which("hipcc") or os.path.exists("/opt/rocm/bin/hipcc")), reason="hipcc not available")
-def test_multi_exponentiation_kernels_use_no_scratch_memory(tmp_path):
+@kernel_resources.needs_hipcc
+def test_multi_exponentiation_kernels_use_no_scratch_memory():
     """every zk_msm_* kernel of the prover, G1 and G2 (the round-5 G2 kernels -- one lane per point, Fq2 products as
     function calls -- sat at 256 VGPRs + 1,168 bytes of scratch, occupancy 1).  Since round 6 G2 runs on lane pairs in lazy limb form:
     no scratch anywhere, the kernels of the mixed additions (level-0 slices, the ones' sums) at 4 wavefronts per SIMD for G1 and 3 for G2
     (no software prefetch of the next base: same or better measured rate, profiles/r06/r06_l, r06_s).  zk_msm_table (once per key: K shifted copies of the bases, canonical-word arithmetic with
     one inversion per copy) is exempt."""
-    info = _resource_usage("zkwg_kernels_msm.hip", tmp_path / "msm.o")
+    info = _resource_usage("zkwg_kernels_msm.hip")
     ks = {n: v for n, v in info.items() if "zk_msm_" in n and "zk_msm_table" not in n}
     assert len(ks) >= 30, sorted(info)
     for n, v in ks.items():
@@ -105,12 +68,12 @@ def test_multi_exponentiation_kernels_use_no_scratch_memory(tmp_path):
     assert all(v["Occupancy"] >= 2 for n, v in ks.items()), ks
 
 
-@pytest.mark.skipif(not (shutil.which("hipcc") or os.path.exists("/opt/rocm/bin/hipcc")), reason="hipcc not available")
-def test_transform_kernels_use_no_scratch_memory_and_keep_their_registers(tmp_path):
+@kernel_resources.needs_hipcc
+def test_transform_kernels_use_no_scratch_memory_and_keep_their_registers():
     """every zk_ntt_* kernel of the prover's transforms: no scratch, and no more VGPRs / no less occupancy than the kernels had before
     their bodies moved into zkwg_ntt_core.h (shared with the host mirror of the CPU tests).  The products keep a 9-limb value and its
     18 partial products in registers; a spill would put them in scratch."""
-    info = _resource_usage("zkwg_kernels_ntt.hip", tmp_path / "ntt.o")
+    info = _resource_usage("zkwg_kernels_ntt.hip")
     ks = {n: v for n, v in info.items() if "zk_ntt_" in n}
     assert len(ks) == 6, sorted(info)
     for n, v in ks.items():

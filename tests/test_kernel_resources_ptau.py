@@ -2,34 +2,12 @@
 GPU: NO SCRATCH MEMORY in any instantiation -- the repository's standing rule for point kernels (tests/test_kernel_resources.py) -- and
 an occupancy of at least zk_phase2_scale's for the same group: 3 wavefronts per SIMD for G1, 2 for G2 (the walk is a chain of dependent
 field products; fewer wavefronts leave its latency exposed)."""
-import os
-import re
-import shutil
-import subprocess
-
-import pytest
-
-from conftest import ROOT
-
-CSRC = os.path.join(ROOT, "zk-email-verify_amd", "csrc")
+import kernel_resources
 
 
-@pytest.mark.skipif(not (shutil.which("hipcc") or os.path.exists("/opt/rocm/bin/hipcc")), reason="hipcc not available")
-def test_ptau_kernels_use_no_scratch_memory_and_keep_the_occupancy_of_phase2(tmp_path):
-    hipcc = shutil.which("hipcc") or "/opt/rocm/bin/hipcc"
-    r = subprocess.run([hipcc, "-O3", "-std=c++17", "--offload-arch=gfx950", "-c", os.path.join(CSRC, "zkwg_kernels_ptau.hip"), "-o", str(tmp_path / "ptau.o"),
-                        "-Rpass-analysis=kernel-resource-usage"], capture_output=True, text=True, timeout=900)
-    assert r.returncode == 0, r.stderr
-    info, cur = {}, None
-    for line in r.stderr.splitlines():
-        m = re.search(r"Function Name: (\S+)", line)
-        if m:
-            cur = m.group(1)
-            info[cur] = {}
-            continue
-        m = re.search(r"remark:\s+([A-Za-z ]+?)(?: \[[^\]]*\])?: (\d+)", line)
-        if m and cur:
-            info[cur][m.group(1).strip()] = int(m.group(2))
+@kernel_resources.needs_hipcc
+def test_ptau_kernels_use_no_scratch_memory_and_keep_the_occupancy_of_phase2():
+    info = kernel_resources.usage("zkwg_kernels_ptau.hip")
     stages = {n: v for n, v in info.items() if "zk_ptau_stage" in n}
     assert len(stages) == 4, sorted(info)                      # G1 / G2 x shared twiddle / twiddle per lane
     assert sum(1 for n in stages if "ZkEcG1" in n) == 2 and sum(1 for n in stages if "ZkEcG2" in n) == 2, sorted(stages)

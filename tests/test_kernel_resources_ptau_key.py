@@ -2,34 +2,12 @@
 cross-compiler, no GPU: NO SCRATCH MEMORY in any instantiation -- the repository's standing rule for point kernels
 (tests/test_kernel_resources.py) -- and the occupancy of the walk kernels: 3 wavefronts per SIMD for G1, 2 for G2 (the walk is a chain of
 dependent field products; fewer wavefronts leave its latency, and here the reads of the table's rows, exposed)."""
-import os
-import re
-import shutil
-import subprocess
-
-import pytest
-
-from conftest import ROOT
-
-CSRC = os.path.join(ROOT, "zk-email-verify_amd", "csrc")
+import kernel_resources
 
 
-@pytest.mark.skipif(not (shutil.which("hipcc") or os.path.exists("/opt/rocm/bin/hipcc")), reason="hipcc not available")
-def test_ptau_key_kernels_use_no_scratch_memory_and_keep_the_occupancy_of_the_walks(tmp_path):
-    hipcc = shutil.which("hipcc") or "/opt/rocm/bin/hipcc"
-    r = subprocess.run([hipcc, "-O3", "-std=c++17", "--offload-arch=gfx950", "-c", os.path.join(CSRC, "zkwg_kernels_ptau_key.hip"), "-o", str(tmp_path / "ptau_key.o"),
-                        "-Rpass-analysis=kernel-resource-usage"], capture_output=True, text=True, timeout=900)
-    assert r.returncode == 0, r.stderr
-    info, cur = {}, None
-    for line in r.stderr.splitlines():
-        m = re.search(r"Function Name: (\S+)", line)
-        if m:
-            cur = m.group(1)
-            info[cur] = {}
-            continue
-        m = re.search(r"remark:\s+([A-Za-z ]+?)(?: \[[^\]]*\])?: (\d+)", line)
-        if m and cur:
-            info[cur][m.group(1).strip()] = int(m.group(2))
+@kernel_resources.needs_hipcc
+def test_ptau_key_kernels_use_no_scratch_memory_and_keep_the_occupancy_of_the_walks():
+    info = kernel_resources.usage("zkwg_kernels_ptau_key.hip")
     walks = {n: v for n, v in info.items() if "zk_ptau_key_walk" in n}
     tables = {n: v for n, v in info.items() if "zk_ptau_key_table" in n}
     assert len(walks) == 4 and len(tables) == 2 and len(info) == 6, sorted(info)      # G1 / G2 x scalars read / computed; every kernel of the file is looked at

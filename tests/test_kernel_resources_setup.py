@@ -2,38 +2,16 @@
 in any of them -- the repository's standing rule for point kernels (tests/test_kernel_resources.py): G2 runs on lane pairs, the exponent
 of the inversion and the table pointers are selected, not indexed, and the batched inversion keeps its prefix products in device memory,
 not in a lane's private array."""
-import os
-import re
-import shutil
-import subprocess
-
-import pytest
-
-from conftest import ROOT
-
-CSRC = os.path.join(ROOT, "zk-email-verify_amd", "csrc")
+import kernel_resources
 
 
-@pytest.mark.skipif(not (shutil.which("hipcc") or os.path.exists("/opt/rocm/bin/hipcc")), reason="hipcc not available")
-def test_setup_kernels_use_no_scratch_memory(tmp_path):
+@kernel_resources.needs_hipcc
+def test_setup_kernels_use_no_scratch_memory():
     """as compiled for gfx950 (ROCm 7), VGPRs / wavefronts per SIMD, <G1> | <G2>: zk_setup_short 211 / 2 | 225 / 2, zk_setup_chunk
     209 / 2 | 224 / 2 (9,216 bytes of LDS: the wavefront's reduction), zk_setup_join_wave 154 / 3 | 167 / 3 (9,216 bytes of LDS),
     zk_setup_den_k 20 / 8 | 40 / 8, zk_setup_affine_k 63 / 8 | 107 / 4, zk_setup_prepare 73 / 6 | 92 / 5; zk_setup_inv_k 61 / 8,
     zk_setup_odd_copy 8 / 8.  Recorded, not asserted: nobody has measured what these kernels need."""
-    hipcc = shutil.which("hipcc") or "/opt/rocm/bin/hipcc"
-    r = subprocess.run([hipcc, "-O3", "-std=c++17", "--offload-arch=gfx950", "-c", os.path.join(CSRC, "zkwg_kernels_setup.hip"), "-o", str(tmp_path / "setup.o"),
-                        "-Rpass-analysis=kernel-resource-usage"], capture_output=True, text=True, timeout=900)
-    assert r.returncode == 0, r.stderr
-    info, cur = {}, None
-    for line in r.stderr.splitlines():
-        m = re.search(r"Function Name: (\S+)", line)
-        if m:
-            cur = m.group(1)
-            info[cur] = {}
-            continue
-        m = re.search(r"remark:\s+([A-Za-z ]+?)(?: \[[^\]]*\])?: (\d+)", line)
-        if m and cur:
-            info[cur][m.group(1).strip()] = int(m.group(2))
+    info = kernel_resources.usage("zkwg_kernels_setup.hip")
     ks = {n: v for n, v in info.items() if "zk_setup_" in n}
     for stem, variants in (("zk_setup_short", 2), ("zk_setup_chunk", 2), ("zk_setup_join_wave", 2), ("zk_setup_den_k", 2), ("zk_setup_affine_k", 2),
                            ("zk_setup_prepare", 2), ("zk_setup_inv_k", 1), ("zk_setup_odd_copy", 1)):

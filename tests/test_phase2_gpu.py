@@ -175,6 +175,26 @@ def test_gpu_point_scale_device_equals_the_known_logarithms_and_the_host_mirror(
     assert phase2test.violations() == 0
 
 
+PIECE = 1 << 20                                   # ZK_PHASE2_PIECE (csrc/zkwg_phase2_core.h): the points of one launch series
+
+
+@pytest.mark.gpu
+def test_gpu_point_scale_device_over_two_pieces_equals_its_single_piece_halves():
+    """piece + 1 points: the smallest call whose piece loop comes round again (its buffers reused, a last piece of one point)"""
+    from zkwg import phase2, ptau
+    rng = random.Random(32)
+    n = PIECE + 1
+    for group, pt in ((1, 64), (2, 128)):
+        t, s = rng.randrange(2, R), rng.randrange(1, R)
+        pts = ptau.point_powers(group, ptau.generators()[group - 1] * n, 1, t)       # t^i G: distinct points, made on the device
+        got = phase2.scale_points(group, pts, s)
+        assert got == phase2.scale_points(group, pts[:pt * PIECE], s) + phase2.scale_points(group, pts[pt * PIECE:], s), group
+        pick = lambda b: b"".join(b[pt * i:pt * i + pt] for i in (0, PIECE - 1, PIECE))
+        assert pick(got) == phase2test.scale(group, pick(pts), s), group
+        del pts, got
+    assert phase2test.violations() == 0
+
+
 @pytest.mark.gpu
 def test_gpu_refusals_and_the_command_line(chain, tmp_path):
     from zkwg import phase2, prove, ptau, setup, wtns, zkey

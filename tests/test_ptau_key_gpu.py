@@ -100,6 +100,35 @@ def test_gpu_in_place_and_a_bad_point_leaves_the_buffer_as_it_was(points):
             ptau.point_mul(group, bytes(bad), scalars)
 
 
+PIECES = {1: 1 << 20, 2: 1 << 19}                 # ZK_KEY_PIECE_G1 / ZK_KEY_PIECE_G2 (csrc/zkwg_ptau_key_core.h): the points of one piece
+
+
+@pytest.mark.gpu
+def test_gpu_point_powers_device_over_two_pieces_equals_its_single_piece_halves():
+    """piece + 1 points: the smallest call that checks every piece first and then brings each to the tables' form again"""
+    import torch
+    from zkwg import _lib, ptau
+    lib = _lib.load()
+    rng = random.Random(64)
+    le = lambda v: int(v).to_bytes(32, "little")
+    for group, pt in ((1, 64), (2, 128)):
+        piece = PIECES[group]
+        n = piece + 1
+        g, t0 = ptau.generators()[group - 1], rng.randrange(2, R)
+        pts = ptau.point_powers(group, g * piece, 1, t0) + ptau.point_powers(group, g, 1, t0, piece)      # t0^i G, from single-piece calls
+        c, t = rng.randrange(1, R), rng.randrange(2, R)
+        whole = ptau.point_powers(group, pts, c, t)
+        assert whole == ptau.point_powers(group, pts[:pt * piece], c, t, 0) + ptau.point_powers(group, pts[pt * piece:], c, t, piece), group
+        at = (0, piece - 1, piece)
+        pick = lambda b: b"".join(b[pt * i:pt * i + pt] for i in at)
+        assert pick(whole) == ptaukeytest.mul(group, pick(pts), [c * pow(t, i, R) % R for i in at]), group
+        d = torch.frombuffer(bytearray(pts), dtype=torch.uint8).cuda()
+        assert lib.zkwg_point_powers_device(0, group, d.data_ptr(), n, le(c), le(t), 0, d.data_ptr(), 0) == 0      # d_out == d_points
+        assert bytes(d.cpu().numpy()) == whole, group
+        del pts, whole, d
+    assert ptaukeytest.violations() == 0
+
+
 @pytest.mark.gpu
 def test_gpu_apply_key_on_a_power_9_file_equals_the_host_mirror():
     from zkwg import ptau

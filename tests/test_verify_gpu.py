@@ -71,6 +71,20 @@ def test_gpu_subgroup_test_equals_the_host_build_and_the_definition(points, outs
     assert verifytest.violations() == 0
 
 
+PIECE = 1 << 20                                   # ZK_VERIFY_PIECE (csrc/zkwg_verify_core.h): the points of one launch of the subgroup test
+
+
+@pytest.mark.gpu
+def test_gpu_subgroup_test_over_two_pieces_counts_and_places_across_them(outside):
+    """piece + 1 points: the smallest call with a second piece, whose flags start afresh and whose index is offset by the piece"""
+    from zkwg import ptau
+    pts = bytearray(ptau.point_powers(2, ptau.generators()[1] * (PIECE + 1), 1, 1114))      # 1114^i G2: distinct points of the subgroup
+    pts[128 * PIECE:] = outside[2]
+    assert ptau.g2_subgroup(bytes(pts)) == (1, PIECE)
+    pts[128 * 5:128 * 6] = outside[2]
+    assert ptau.g2_subgroup(bytes(pts)) == (2, 5)
+
+
 def _scalars(rng, n, bits=128):
     top = (1 << bits) - 1 if bits == 128 else R - 1
     s = [rng.randrange(top + 1) for _ in range(n)]

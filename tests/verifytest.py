@@ -2,29 +2,17 @@
 (tests/native/verifytest.cpp) -- the G2 subgroup test as a lane pair of the kernel runs it and the pairing product -- and the twist points
 outside the subgroup that the subgroup tests share."""
 import ctypes as C
-import os
-import subprocess
 
-from conftest import ROOT
+import nativelib
 
 R = 21888242871839275222246405745257275088548364400416034343698204186575808495617
 Q = 21888242871839275222246405745257275088696311157297823662689037894645226208583
 COFACTOR = 2 * Q - R                       # of the twist: 10069 x 5864401 x (a large factor)
 SMALL = (10069, 5864401, 10069 * 5864401)
-_SO = os.path.join(ROOT, "tests", "native", "libzkwg_verifytest.so")
-_SRC = os.path.join(ROOT, "tests", "native", "verifytest.cpp")
-_CSRC = os.path.join(ROOT, "zk-email-verify_amd", "csrc")
-_lib = None
 
 
 def load():
-    global _lib
-    if _lib is not None:
-        return _lib
-    deps = [_SRC, os.path.join(ROOT, "include", "zkwg.h")] + [os.path.join(_CSRC, f) for f in os.listdir(_CSRC) if f.endswith(".h")]
-    if not os.path.exists(_SO) or any(os.path.getmtime(d) > os.path.getmtime(_SO) for d in deps):
-        subprocess.check_call(["g++", "-O2", "-std=c++17", "-shared", "-fPIC", "-I", _CSRC, _SRC, "-o", _SO])
-    lib = C.CDLL(_SO)
+    lib = nativelib.build("verifytest")
     u64, u32 = C.c_uint64, C.c_uint32
     lib.vt_violations.restype = C.c_ulonglong
     lib.vt_u_digits.restype = None
@@ -37,7 +25,6 @@ def load():
     lib.vt_pairing_check.argtypes = [C.c_char_p, C.c_char_p, u32, C.POINTER(C.c_int), C.c_char_p, u64]
     lib.vt_rlc.restype = C.c_int
     lib.vt_rlc.argtypes = [C.c_int, C.c_char_p, u64, C.c_char_p, u32, C.c_void_p]
-    _lib = lib
     return lib
 
 

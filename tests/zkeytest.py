@@ -1,23 +1,15 @@
 """Test-only helpers of the prover of witnesses: the host build of csrc/zkwg_zkey_core.h (tests/native/zkeytest.cpp) and a seeded random
 constraint system that is not an email circuit."""
 import ctypes as C
-import os
 import random
-import subprocess
 
-from conftest import ROOT
+import nativelib
 
 R = 21888242871839275222246405745257275088548364400416034343698204186575808495617
-_SO = os.path.join(ROOT, "tests", "native", "libzkwg_zkeytest.so")
-_SRC = os.path.join(ROOT, "tests", "native", "zkeytest.cpp")
-_CSRC = os.path.join(ROOT, "zk-email-verify_amd", "csrc")
 
 
 def load():
-    deps = [_SRC, os.path.join(ROOT, "include", "zkwg.h")] + [os.path.join(_CSRC, f) for f in os.listdir(_CSRC) if f.endswith(".h")]
-    if not os.path.exists(_SO) or any(os.path.getmtime(d) > os.path.getmtime(_SO) for d in deps):
-        subprocess.check_call(["g++", "-O2", "-std=c++17", "-shared", "-fPIC", "-I", _CSRC, _SRC, "-o", _SO])
-    lib = C.CDLL(_SO)
+    lib = nativelib.build("zkeytest")
     u64p = C.POINTER(C.c_uint64)
     lib.zt_violations.restype = C.c_ulonglong
     lib.zt_zkey_check.restype = C.c_int

@@ -32,7 +32,7 @@ PREDICTED_RATIO = (62 * 9 + 23 * 10 + (10 + 2 * 14 + 9) + 9 + 4) / (254 * 9 + 73
 def _twist_point_outside(seed):
     """a point of the twist by try-and-increment, the cofactor not cleared, and its multiple of order 10069 (bytes in the zkey's form)"""
     import hashlib
-    from zkwg import phase2
+    from zkwg import _call, phase2
     from zkwg.zkey import Q, R
     for counter in range(1 << 16):
         h = [hashlib.blake2b(seed + bytes([counter & 255, counter >> 8, half]), digest_size=64).digest() for half in (0, 1)]
@@ -41,7 +41,7 @@ def _twist_point_outside(seed):
         y = phase2._f2_sqrt(((x3[0] + phase2._B2[0]) % Q, (x3[1] + phase2._B2[1]) % Q))
         if y is None:
             continue
-        raw = b"".join(phase2._mont(v) for v in (x[0], x[1], y[0], y[1]))
+        raw = b"".join(_call.mont(v) for v in (x[0], x[1], y[0], y[1]))
         small = phase2.scale_points(2, phase2.scale_points(2, raw, R), (2 * Q - R) // 10069)
         if any(small):
             return raw, small

@@ -4,114 +4,79 @@
 // point on its curve before anything is written, run every piece through
 //   tables' form -> zk_ptau_key_table -> affine -> tables' form -> zk_ptau_key_walk -> affine
 // synchronise and free everything before they return.
-#include <hip/hip_runtime.h>
 #include <string.h>
-#include <chrono>
-#include <string>
-#include <vector>
-#include "../../include/zkwg.h"
 #include "zkwg_ptau_key_core.h"
-
-void zk_ptau_key_table_launch(int group, const void* tab, void* acc, u32 n, hipStream_t st);                              // zkwg_kernels_ptau_key.hip
-void zk_ptau_key_walk_launch(int group, const void* tab, void* acc, u32 n, const void* scalars, const ZkKeyPowers* powers, u64 first, hipStream_t st);
-void zk_setup_prepare_launch(int group, const void* in, void* out, u64 n, u32* bad, hipStream_t st);                      // zkwg_kernels_setup.hip
-void zk_setup_to_affine_launch(int group, const void* acc, Fq29* den, Fq29* pref, const u32* seg_wire, void* out, u32 n, hipStream_t st);
-extern "C" void zk_set_last_error(const char* m);                                                                           // zkwg_api.hip
+#include "zkwg_points_host.h"
 
 namespace {
-thread_local double g_seconds[18];
-thread_local u64 g_ops[8];
-int fail(const std::string& m) { zk_set_last_error(m.c_str()); return ZKWG_RC_BAD_CONFIG; }
-double now() { return std::chrono::duration<double>(std::chrono::steady_clock::now().time_since_epoch()).count(); }
-const char* const NOT_ON_CURVE = "a point is not on its curve (or not reduced)";
+thread_local ZkStats<18, 8> g_stats;
 
-// the buffers of one piece of at most n points
-struct Piece {
-  void *tab = nullptr, *acc = nullptr, *stage = nullptr;       // the table T[row][point]; the accumulators of rows 1 - 7; host points of a piece
-  Fq29 *den = nullptr, *pref = nullptr;
-  ZkKeyPowers* powers = nullptr;
-  u32* bad = nullptr;                   // [0]: an input point failed its check; [1]: a row of a table did (never: an internal error)
-  int alloc(int group, u64 n, bool with_stage) {
-    const u64 pt = group == 2 ? 128 : 64, xs = group == 2 ? 288 : 144, rows = ZK_KEY_ROWS - 1;
-    if (hipMalloc(&tab, ZK_KEY_ROWS * n * pt) != hipSuccess || hipMalloc(&acc, rows * n * xs) != hipSuccess || hipMalloc((void**)&den, rows * n * sizeof(Fq29)) != hipSuccess ||
-        hipMalloc((void**)&pref, rows * n * sizeof(Fq29)) != hipSuccess || hipMalloc((void**)&powers, sizeof(ZkKeyPowers)) != hipSuccess ||
-        hipMalloc((void**)&bad, 8) != hipSuccess || (with_stage && hipMalloc(&stage, n * pt) != hipSuccess)) {
-      (void)hipGetLastError();
-      return ZKWG_RC_OOM;
-    }
-    return hipMemset(bad, 0, 8) == hipSuccess ? ZKWG_RC_OK : ZKWG_RC_HIP_ERROR;
-  }
-  ~Piece() { hipFree(tab); hipFree(acc); hipFree(stage); hipFree(den); hipFree(pref); hipFree(powers); hipFree(bad); }
-};
 // out[i] = k_i in[i], n points; k_i = scalars[i] (device memory, 32 bytes each), or c t^(first + i) from T when scalars is null.
 // in / out: device memory (on_device) or host memory, staged through the piece.  seconds (may be null): {upload + curve check, tables,
 // walk, conversion + download} are added to seconds[0 .. 3], a synchronisation after each stage.
 int mul_points(int group, const void* in, u64 n, const void* scalars, const ZkKeyPowers* T, u64 first, void* out, bool on_device, hipStream_t st, double* seconds) {
   if (!n) return ZKWG_RC_OK;
-  const u64 pt = group == 2 ? 128 : 64, piece = group == 2 ? ZK_KEY_PIECE_G2 : ZK_KEY_PIECE_G1;
-  Piece B;
-  int rc = B.alloc(group, std::min<u64>(n, piece), !on_device);
-  if (rc != ZKWG_RC_OK) return rc;
-  if (T && hipMemcpyAsync(B.powers, T, sizeof(ZkKeyPowers), hipMemcpyHostToDevice, st) != hipSuccess) return ZKWG_RC_HIP_ERROR;
+  const u64 pt = zk_pt_bytes(group), xs = zk_acc_bytes(group), piece = group == 2 ? ZK_KEY_PIECE_G2 : ZK_KEY_PIECE_G1;
+  const u64 cap = std::min<u64>(n, piece), rows_n = (ZK_KEY_ROWS - 1) * cap;
+  // the buffers of one piece: the table T[row][point]; the accumulators of rows 1 - 7; the host points of a piece
+  DevBufs B;
+  void *tab = B.get(ZK_KEY_ROWS * cap * pt), *acc = B.get(rows_n * xs);
+  Fq29 *den = (Fq29*)B.get(rows_n * sizeof(Fq29)), *pref = (Fq29*)B.get(rows_n * sizeof(Fq29));
+  ZkKeyPowers* powers = (ZkKeyPowers*)B.get(sizeof(ZkKeyPowers));
+  u32* d_bad = (u32*)B.get(8);          // [0]: an input point failed its check; [1]: a row of a table did (never: an internal error)
+  void* stage = on_device ? nullptr : B.get(cap * pt);
+  if (B.oom) return ZKWG_RC_OOM;
+  if (hipMemset(d_bad, 0, 8) != hipSuccess) return ZKWG_RC_HIP_ERROR;
+  if (T && hipMemcpyAsync(powers, T, sizeof(ZkKeyPowers), hipMemcpyHostToDevice, st) != hipSuccess) return ZKWG_RC_HIP_ERROR;
   u32 bad[2] = {0, 0};
-  auto flags = [&]() { return hipGetLastError() == hipSuccess && hipMemcpyAsync(bad, B.bad, 8, hipMemcpyDeviceToHost, st) == hipSuccess && hipStreamSynchronize(st) == hipSuccess; };
-  double t = now();
+  ZkStageClock clock(st, seconds);
   // every point is checked before the first is written (out may be in: a refusal leaves the points as they were)
   for (u64 at = 0; at < n; at += piece) {
     const u64 m = std::min<u64>(piece, n - at);
     const u8* src = (const u8*)in + at * pt;
-    if (!on_device && hipMemcpyAsync(B.stage, src, m * pt, hipMemcpyHostToDevice, st) != hipSuccess) return ZKWG_RC_HIP_ERROR;
-    zk_setup_prepare_launch(group, on_device ? (const void*)src : B.stage, B.tab, m, B.bad, st);
+    if (!on_device && hipMemcpyAsync(stage, src, m * pt, hipMemcpyHostToDevice, st) != hipSuccess) return ZKWG_RC_HIP_ERROR;
+    zk_setup_prepare_launch(group, on_device ? (const void*)src : stage, tab, m, d_bad, st);
   }
-  if (!flags()) return ZKWG_RC_HIP_ERROR;
+  if (zk_read_flags(st, d_bad, bad, 2) != ZKWG_RC_OK) return ZKWG_RC_HIP_ERROR;
   if (bad[0]) return fail(NOT_ON_CURVE);
-  auto stage = [&](int k) {
-    if (!seconds) return true;
-    if (hipStreamSynchronize(st) != hipSuccess) return false;
-    seconds[k] += now() - t; t = now();
-    return true;
-  };
-  if (!stage(0)) return ZKWG_RC_HIP_ERROR;
+  if (!clock.lap(0)) return ZKWG_RC_HIP_ERROR;
   for (u64 at = 0; at < n; at += piece) {
     const u32 m = (u32)std::min<u64>(piece, n - at);
     const u8* src = (const u8*)in + at * pt;
     u8* dst = (u8*)out + at * pt;
-    u8* rows = (u8*)B.tab + (u64)m * pt;                            // rows 1 - 7
+    u8* rows = (u8*)tab + (u64)m * pt;                              // rows 1 - 7
     if (n > piece) {                                                // (a single piece is in row 0 since its check)
-      if (!on_device && hipMemcpyAsync(B.stage, src, m * pt, hipMemcpyHostToDevice, st) != hipSuccess) return ZKWG_RC_HIP_ERROR;
-      zk_setup_prepare_launch(group, on_device ? (const void*)src : B.stage, B.tab, m, B.bad, st);
+      if (!on_device && hipMemcpyAsync(stage, src, m * pt, hipMemcpyHostToDevice, st) != hipSuccess) return ZKWG_RC_HIP_ERROR;
+      zk_setup_prepare_launch(group, on_device ? (const void*)src : stage, tab, m, d_bad, st);
     }
-    if (!stage(0)) return ZKWG_RC_HIP_ERROR;
-    zk_ptau_key_table_launch(group, B.tab, B.acc, m, st);
-    zk_setup_to_affine_launch(group, B.acc, B.den, B.pref, nullptr, rows, (ZK_KEY_ROWS - 1) * m, st);
-    zk_setup_prepare_launch(group, rows, rows, (u64)(ZK_KEY_ROWS - 1) * m, B.bad + 1, st);
-    if (!stage(1)) return ZKWG_RC_HIP_ERROR;
-    zk_ptau_key_walk_launch(group, B.tab, B.acc, m, scalars ? (const u8*)scalars + at * 32 : nullptr, B.powers, first + at, st);
-    if (!stage(2)) return ZKWG_RC_HIP_ERROR;
-    zk_setup_to_affine_launch(group, B.acc, B.den, B.pref, nullptr, on_device ? (void*)dst : B.stage, m, st);
-    if (!on_device && (hipMemcpyAsync(dst, B.stage, m * pt, hipMemcpyDeviceToHost, st) != hipSuccess || hipStreamSynchronize(st) != hipSuccess)) return ZKWG_RC_HIP_ERROR;
-    if (!stage(3)) return ZKWG_RC_HIP_ERROR;
+    if (!clock.lap(0)) return ZKWG_RC_HIP_ERROR;
+    zk_ptau_key_table_launch(group, tab, acc, m, st);
+    zk_setup_to_affine_launch(group, acc, den, pref, nullptr, rows, (ZK_KEY_ROWS - 1) * m, st);
+    zk_setup_prepare_launch(group, rows, rows, (u64)(ZK_KEY_ROWS - 1) * m, d_bad + 1, st);
+    if (!clock.lap(1)) return ZKWG_RC_HIP_ERROR;
+    zk_ptau_key_walk_launch(group, tab, acc, m, scalars ? (const u8*)scalars + at * 32 : nullptr, powers, first + at, st);
+    if (!clock.lap(2)) return ZKWG_RC_HIP_ERROR;
+    zk_setup_to_affine_launch(group, acc, den, pref, nullptr, on_device ? (void*)dst : stage, m, st);
+    if (!on_device && (hipMemcpyAsync(dst, stage, m * pt, hipMemcpyDeviceToHost, st) != hipSuccess || hipStreamSynchronize(st) != hipSuccess)) return ZKWG_RC_HIP_ERROR;
+    if (!clock.lap(3)) return ZKWG_RC_HIP_ERROR;
   }
-  if (!flags()) return ZKWG_RC_HIP_ERROR;
+  if (zk_read_flags(st, d_bad, bad, 2) != ZKWG_RC_OK) return ZKWG_RC_HIP_ERROR;
   if (bad[1]) { zk_set_last_error("internal: a row of a point's table is not on its curve"); return ZKWG_RC_HIP_ERROR; }
   return ZKWG_RC_OK;
-}
-bool bad_args(int group, const void* d_points, u64 n, const void* d_out) {
-  return (group != 1 && group != 2) || (n && (!d_points || !d_out)) || ((uintptr_t)d_points & 15) || ((uintptr_t)d_out & 15);
 }
 }  // namespace
 
 extern "C" {
 
 int zkwg_point_mul_device(int device, int group, const void* d_points, uint64_t n, const void* d_scalars, void* d_out, void* hip_stream) {
-  if (bad_args(group, d_points, n, d_out) || (n && !d_scalars) || ((uintptr_t)d_scalars & 15)) return ZKWG_RC_BAD_ARG;
+  if (zk_bad_point_args(group, d_points, n, d_out) || (n && !d_scalars) || ((uintptr_t)d_scalars & 15)) return ZKWG_RC_BAD_ARG;
   if (device < 0) return ZKWG_RC_NO_DEVICE;
   if (hipSetDevice(device) != hipSuccess) return ZKWG_RC_HIP_ERROR;
   return mul_points(group, d_points, n, d_scalars, nullptr, 0, d_out, true, (hipStream_t)hip_stream, nullptr);
 }
 
 int zkwg_point_powers_device(int device, int group, const void* d_points, uint64_t n, const uint8_t* c, const uint8_t* t, uint64_t first, void* d_out, void* hip_stream) {
-  if (bad_args(group, d_points, n, d_out) || !c || !t || first + n < first) return ZKWG_RC_BAD_ARG;
+  if (zk_bad_point_args(group, d_points, n, d_out) || !c || !t || first + n < first) return ZKWG_RC_BAD_ARG;
   if (device < 0) return ZKWG_RC_NO_DEVICE;
   ZkKeyPowers T;
   if (!zk_key_powers_table(c, t, T)) return fail("the scalars c and t must not be 0 modulo the group order");
@@ -133,8 +98,7 @@ int zkwg_ptau_apply_key(int device, const uint8_t* ptau, uint64_t len, const uin
   if (!ptau || !tau || !alpha || !beta || !out || (section7_len && !section7)) return ZKWG_RC_BAD_ARG;
   if (device < 0) return ZKWG_RC_NO_DEVICE;
   try {
-    for (double& s : g_seconds) s = 0;
-    for (u64& o : g_ops) o = 0;
+    g_stats.reset();
     double t0 = now();
     ZkPtauKeyFrame F;
     std::string err;
@@ -144,20 +108,23 @@ int zkwg_ptau_apply_key(int device, const uint8_t* ptau, uint64_t len, const uin
     if (zk_ptau_key_scalars(tau, alpha, beta, K, err) != ZKWG_RC_OK) return fail(err);
     if (hipSetDevice(device) != hipSuccess) return ZKWG_RC_HIP_ERROR;
     const int rc = zk_ptau_key_apply(ptau, F, K, section7, out, [&](int group, const u8* in, u64 count, const u8* c, const u8* t, u8* o, int section) {
-      if (section == 2) g_seconds[16] = now() - t0;            // (the first call comes after the copies of sections 1 and 7)
+      if (section == 2) g_stats.seconds[16] = now() - t0;      // (the first call comes after the copies of sections 1 and 7)
       ZkKeyPowers T;
       zk_key_powers_table(c, t, T);                            // (neither is 0: zk_ptau_key_scalars)
-      g_ops[2 * (section - 2)] = count * ZK_KEY_ADDS_PER_POINT; g_ops[2 * (section - 2) + 1] = count * ZK_KEY_DBLS_PER_POINT;
-      return mul_points(group, in, count, nullptr, &T, 0, o, false, nullptr, g_seconds + 4 * (section - 2));
+      g_stats.ops[2 * (section - 2)] = count * ZK_KEY_ADDS_PER_POINT; g_stats.ops[2 * (section - 2) + 1] = count * ZK_KEY_DBLS_PER_POINT;
+      return mul_points(group, in, count, nullptr, &T, 0, o, false, nullptr, g_stats.seconds + 4 * (section - 2));
     }, [&](const u8* in, const u8* k, u8* o) {
       const double t = now();
-      void* d = nullptr;
-      if (hipMalloc(&d, 128) != hipSuccess) { (void)hipGetLastError(); return (int)ZKWG_RC_OOM; }
-      int r = hipMemcpy(d, in, 128, hipMemcpyHostToDevice) == hipSuccess ? ZKWG_RC_OK : ZKWG_RC_HIP_ERROR;
-      if (r == ZKWG_RC_OK) r = zkwg_point_scale_device(device, 2, d, 1, k, d, nullptr);
-      if (r == ZKWG_RC_OK && hipMemcpy(o, d, 128, hipMemcpyDeviceToHost) != hipSuccess) r = ZKWG_RC_HIP_ERROR;
-      hipFree(d);
-      g_seconds[17] = now() - t;
+      int r;
+      {
+        DevBufs B;
+        void* d = B.get(128);
+        if (B.oom) return (int)ZKWG_RC_OOM;
+        r = hipMemcpy(d, in, 128, hipMemcpyHostToDevice) == hipSuccess ? ZKWG_RC_OK : ZKWG_RC_HIP_ERROR;
+        if (r == ZKWG_RC_OK) r = zkwg_point_scale_device(device, 2, d, 1, k, d, nullptr);
+        if (r == ZKWG_RC_OK && hipMemcpy(o, d, 128, hipMemcpyDeviceToHost) != hipSuccess) r = ZKWG_RC_HIP_ERROR;
+      }                                                          // (freed before the time is taken)
+      g_stats.seconds[17] = now() - t;
       return r;
     });
     if (rc == ZKWG_RC_OK && out_len) *out_len = F.out_bytes;
@@ -168,8 +135,7 @@ int zkwg_ptau_apply_key(int device, const uint8_t* ptau, uint64_t len, const uin
 }
 
 void zkwg_ptau_apply_key_stats(double seconds[18], uint64_t ops[8]) {
-  if (seconds) for (int i = 0; i < 18; ++i) seconds[i] = g_seconds[i];
-  if (ops) for (int i = 0; i < 8; ++i) ops[i] = g_ops[i];
+  g_stats.copy(seconds, ops);
 }
 
 }

@@ -1,45 +1,16 @@
 // C-ABI of the groth16 set-up (include/zkwg.h "the groth16 set-up"): zkwg_ptau_parse, zkwg_zkey_new_size, zkwg_zkey_new.
 // zkwg_zkey_new is a one-shot call: it allocates its device buffers, synchronises after every stage (that is where its times come from)
 // and frees everything before it returns -- a key is made once per circuit.
-#include <hip/hip_runtime.h>
 #include <string.h>
-#include <chrono>
-#include <string>
-#include <vector>
-#include "../../include/zkwg.h"
-#include "zkwg_setup_core.h"
-
-void zk_setup_run_launch(int group, const ZkSetupRun& r, hipStream_t st);                         // zkwg_kernels_setup.hip
-void zk_setup_prepare_launch(int group, const void* in, void* out, u64 n, u32* bad, hipStream_t st);
-void zk_setup_odd_copy_launch(const void* in, void* out, u64 n, hipStream_t st);
-extern "C" void zk_set_last_error(const char* m);                                                   // zkwg_api.hip
+#include "zkwg_points_host.h"
 
 namespace {
-struct DevBufs {
-  std::vector<void*> p;
-  bool oom = false;
-  void* get(u64 bytes) {
-    void* d = nullptr;
-    if (hipMalloc(&d, bytes ? bytes : 16) != hipSuccess) { oom = true; return nullptr; }
-    p.push_back(d);
-    return d;
-  }
-  template <class T> T* up(const std::vector<T>& v) {
-    T* d = (T*)get(v.size() * sizeof(T));
-    if (d && !v.empty() && hipMemcpy(d, v.data(), v.size() * sizeof(T), hipMemcpyHostToDevice) != hipSuccess) oom = true;
-    return d;
-  }
-  ~DevBufs() { for (void* d : p) hipFree(d); }
-};
-thread_local double g_seconds[7];
-thread_local u64 g_ops[8];
-int fail(const std::string& m) { zk_set_last_error(m.c_str()); return ZKWG_RC_BAD_CONFIG; }
-double now() { return std::chrono::duration<double>(std::chrono::steady_clock::now().time_since_epoch()).count(); }
+thread_local ZkStats<7, 8> g_stats;
 
 // one sum: plan -> the n_vars points of a section, downloaded to `host_out` (point bytes: 64 / 128)
 int run_plan(int group, const ZkSetupPlan& P, const ZkSetupMag* d_mag, const void* t0, const void* t1, const void* t2, u32 n_vars, u8* host_out) {
   DevBufs B;
-  const u64 pt = group == 2 ? 128 : 64, xs = group == 2 ? 288 : 144, n_seg = P.seg_wire.size();
+  const u64 pt = zk_pt_bytes(group), xs = zk_acc_bytes(group), n_seg = P.seg_wire.size();
   ZkSetupRun r;
   r.T = ZkSetupDev{B.up(P.terms), d_mag};
   r.t0 = t0; r.t1 = t1; r.t2 = t2;
@@ -88,8 +59,7 @@ int zkwg_zkey_new(int device, const uint8_t* r1cs, uint64_t len, const zkwg_setu
   if (!r1cs || !sl || !out_zkey || !sl->tau_g1 || !sl->tau_g2 || !sl->alpha_tau_g1 || !sl->beta_tau_g1 || !sl->tau_g1_next) return ZKWG_RC_BAD_ARG;
   if (device < 0) return ZKWG_RC_NO_DEVICE;
   try {
-    for (double& s : g_seconds) s = 0;
-    for (u64& o : g_ops) o = 0;
+    g_stats.reset();
     double t = now();
     ZkR1csHost R;
     if (!zk_r1cs_parse(r1cs, len, R)) return fail("the .r1cs file could not be parsed: " + R.err);
@@ -107,8 +77,8 @@ int zkwg_zkey_new(int device, const uint8_t* r1cs, uint64_t len, const zkwg_setu
     ZkSetupLayout L;
     zk_setup_write_frame(R, S, *sl, out_zkey, L);
     const ZkSetupPlan* plans[4] = {&pa, &pb, &pb, &pk};
-    for (int i = 0; i < 4; ++i) { g_ops[2 * i] = plans[i]->n_add; g_ops[2 * i + 1] = plans[i]->n_dbl; }
-    g_seconds[0] = now() - t; t = now();
+    for (int i = 0; i < 4; ++i) { g_stats.ops[2 * i] = plans[i]->n_add; g_stats.ops[2 * i + 1] = plans[i]->n_dbl; }
+    g_stats.seconds[0] = now() - t; t = now();
 
     if (hipSetDevice(device) != hipSuccess) return ZKWG_RC_HIP_ERROR;
     DevBufs B;
@@ -125,7 +95,7 @@ int zkwg_zkey_new(int device, const uint8_t* r1cs, uint64_t len, const zkwg_setu
     for (const Slice& s : slices) {
       const void* src = s.p;
       if (!sl->on_device) {
-        if (hipMemcpy(d_stage, s.p, s.count * (s.group == 2 ? 128 : 64), hipMemcpyHostToDevice) != hipSuccess) return ZKWG_RC_HIP_ERROR;
+        if (hipMemcpy(d_stage, s.p, s.count * zk_pt_bytes(s.group), hipMemcpyHostToDevice) != hipSuccess) return ZKWG_RC_HIP_ERROR;
         src = d_stage;
         d_next = d_stage;
       }
@@ -137,24 +107,24 @@ int zkwg_zkey_new(int device, const uint8_t* r1cs, uint64_t len, const zkwg_setu
     if (bad) return fail("a point of the powers of tau is not on its curve (or not reduced)");
     const ZkSetupMag* d_mag = B.up(M.mag);
     if (B.oom) return ZKWG_RC_OOM;
-    g_seconds[1] = now() - t; t = now();
+    g_stats.seconds[1] = now() - t; t = now();
 
     std::vector<u8> sec((size_t)64 * S.n_vars);
     int rc = run_plan(1, pa, d_mag, d_t1, nullptr, nullptr, S.n_vars, out_zkey + L.off[5]);
-    g_seconds[2] = now() - t; t = now();
+    g_stats.seconds[2] = now() - t; t = now();
     if (rc == ZKWG_RC_OK) rc = run_plan(1, pb, d_mag, d_t1, nullptr, nullptr, S.n_vars, out_zkey + L.off[6]);
-    g_seconds[3] = now() - t; t = now();
+    g_stats.seconds[3] = now() - t; t = now();
     if (rc == ZKWG_RC_OK) rc = run_plan(2, pb, d_mag, d_t2, nullptr, nullptr, S.n_vars, out_zkey + L.off[7]);
-    g_seconds[4] = now() - t; t = now();
+    g_stats.seconds[4] = now() - t; t = now();
     if (rc == ZKWG_RC_OK) rc = run_plan(1, pk, d_mag, d_t1, d_tb, d_ta, S.n_vars, sec.data());
-    g_seconds[5] = now() - t; t = now();
+    g_stats.seconds[5] = now() - t; t = now();
     if (rc != ZKWG_RC_OK) return rc;
     memcpy(out_zkey + L.off[3], sec.data(), 64ull * (S.n_public + 1));
     memcpy(out_zkey + L.off[8], sec.data() + 64ull * (S.n_public + 1), 64ull * (S.n_vars - S.n_public - 1));
     // section 9: the odd entries of level p + 1 (d_t1 is free now)
     zk_setup_odd_copy_launch(d_next, d_t1, n, nullptr);
     if (hipGetLastError() != hipSuccess || hipMemcpy(out_zkey + L.off[9], d_t1, 64 * n, hipMemcpyDeviceToHost) != hipSuccess) return ZKWG_RC_HIP_ERROR;
-    g_seconds[6] = now() - t;
+    g_stats.seconds[6] = now() - t;
     if (out_len) *out_len = S.zkey_bytes;
     return ZKWG_RC_OK;
   } catch (const std::bad_alloc&) {
@@ -163,8 +133,7 @@ int zkwg_zkey_new(int device, const uint8_t* r1cs, uint64_t len, const zkwg_setu
 }
 
 void zkwg_zkey_new_stats(double seconds[7], uint64_t ops[8]) {
-  if (seconds) for (int i = 0; i < 7; ++i) seconds[i] = g_seconds[i];
-  if (ops) for (int i = 0; i < 8; ++i) ops[i] = g_ops[i];
+  g_stats.copy(seconds, ops);
 }
 
 }

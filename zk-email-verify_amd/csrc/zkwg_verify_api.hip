@@ -7,28 +7,18 @@
 // bases on the device and a table budget too small for shifted copies: K bucket sets and a Horner pass -- right for bases used once).
 // The plan converts its piece of the points into a table of its own, so the two arrays of a call may overlap (d_b = d_a + one point: the
 // shifted form of the powers checks); the partial sums of the pieces are added on the host (zkwg_g1.h / zkwg_g2.h).
-#include <hip/hip_runtime.h>
 #include <string.h>
 #include <algorithm>
-#include <string>
-#include "../../include/zkwg.h"
 #include "zkwg_pairing.h"
-
-void zk_verify_g2_subgroup_launch(const void* pts, u32 n, const ZkPhase2Digits& Du, u32* res, hipStream_t st);          // zkwg_kernels_verify.hip
-void zk_verify_widen_launch(const void* in, void* out, u64 n, hipStream_t st);
-void zk_setup_prepare_launch(int group, const void* in, void* out, u64 n, u32* bad, hipStream_t st);                     // zkwg_kernels_setup.hip
-extern "C" void zk_set_last_error(const char* m);                                                                          // zkwg_api.hip
+#include "zkwg_points_host.h"
 
 namespace {
-int fail(const std::string& m) { zk_set_last_error(m.c_str()); return ZKWG_RC_BAD_CONFIG; }
-const char* const NOT_ON_CURVE = "a point is not on its curve (or not reduced)";
 #define ZK_VERIFY_RLC_PIECE (1ull << 22)
 
-struct Buffers {
-  void *tab = nullptr, *wide = nullptr, *work = nullptr;
-  u32* flags = nullptr;
-  zkwg_msm_t* plan = nullptr;
-  ~Buffers() { if (plan) zkwg_msm_destroy(plan); hipFree(tab); hipFree(wide); hipFree(work); hipFree(flags); }
+// the multi-exponentiation plan of one piece: destroyed on every way out
+struct Plan {
+  zkwg_msm_t* p = nullptr;
+  ~Plan() { if (p) zkwg_msm_destroy(p); }
 };
 
 // the host accumulator of the pieces' partial sums
@@ -46,41 +36,43 @@ struct Sum {
 };
 
 int rlc(int device, int group, const void* d_a, const void* d_b, u64 n, const void* d_scalars, u32 scalar_bytes, u64 piece_points, u8* out_a, u8* out_b, hipStream_t st) {
-  const u64 pt = group == 2 ? 128 : 64;
-  if ((group != 1 && group != 2) || !out_a || (d_b && !out_b) || (n && (!d_a || !d_scalars)) || ((uintptr_t)d_a & 15) || ((uintptr_t)d_b & 15) || ((uintptr_t)d_scalars & 15) ||
-      piece_points >= (1ull << 31))
-    return ZKWG_RC_BAD_ARG;
+  const u64 pt = zk_pt_bytes(group);
+  if (zk_bad_point_args(group, d_a, n, d_scalars) || !out_a || (d_b && !out_b) || ((uintptr_t)d_b & 15) || piece_points >= (1ull << 31)) return ZKWG_RC_BAD_ARG;
   if (device < 0) return ZKWG_RC_NO_DEVICE;
   if (hipSetDevice(device) != hipSuccess) return ZKWG_RC_HIP_ERROR;
   const u64 piece = piece_points ? piece_points : ZK_VERIFY_RLC_PIECE;
   Sum sa, sb;
   if (n) {
-    Buffers B;
-    if (hipMalloc((void**)&B.flags, 4) != hipSuccess || (scalar_bytes == 16 && hipMalloc(&B.wide, std::min(n, piece) * 32) != hipSuccess)) { (void)hipGetLastError(); return ZKWG_RC_OOM; }
-    if (hipMemsetAsync(B.flags, 0, 4, st) != hipSuccess) return ZKWG_RC_HIP_ERROR;
+    DevBufs B;
+    Plan plan;
+    u32* d_bad = (u32*)B.get(4);
+    void *wide = scalar_bytes == 16 ? B.get(std::min(n, piece) * 32) : nullptr, *work = nullptr;
+    if (B.oom) return ZKWG_RC_OOM;
+    if (hipMemsetAsync(d_bad, 0, 4, st) != hipSuccess) return ZKWG_RC_HIP_ERROR;
     // every point of both arrays is checked before anything is summed
-    zk_setup_prepare_launch(group, d_a, nullptr, n, B.flags, st);
-    if (d_b) zk_setup_prepare_launch(group, d_b, nullptr, n, B.flags, st);
+    zk_setup_prepare_launch(group, d_a, nullptr, n, d_bad, st);
+    if (d_b) zk_setup_prepare_launch(group, d_b, nullptr, n, d_bad, st);
     u32 bad = 0;
-    if (hipGetLastError() != hipSuccess || hipMemcpyAsync(&bad, B.flags, 4, hipMemcpyDeviceToHost, st) != hipSuccess || hipStreamSynchronize(st) != hipSuccess) return ZKWG_RC_HIP_ERROR;
+    if (zk_read_flags(st, d_bad, &bad, 1) != ZKWG_RC_OK) return ZKWG_RC_HIP_ERROR;
     if (bad) return fail(NOT_ON_CURVE);
     u64 work_for = 0;
     for (u64 at = 0; at < n; at += piece) {
       const u64 m = std::min(piece, n - at);
       const void* s = (const u8*)d_scalars + at * scalar_bytes;
-      if (scalar_bytes == 16) { zk_verify_widen_launch(s, B.wide, m, st); s = B.wide; }
+      if (scalar_bytes == 16) { zk_verify_widen_launch(s, wide, m, st); s = wide; }
       for (int which = 0; which < (d_b ? 2 : 1); ++which) {
         const u8* base = (const u8*)(which ? d_b : d_a) + at * pt;
-        int rc = zkwg_msm_create_ex(device, group, base, 1, m, 0, 0, 1, &B.plan);       // (a budget of one byte: the classic layout)
+        int rc = zkwg_msm_create_ex(device, group, base, 1, m, 0, 0, 1, &plan.p);       // (a budget of one byte: the classic layout)
         if (rc != ZKWG_RC_OK) return rc;
         if (work_for != m) {                                                           // (the layout depends on the group and the count only)
-          hipFree(B.work); B.work = nullptr;
-          if (hipMalloc(&B.work, zkwg_msm_work_bytes(B.plan)) != hipSuccess) { (void)hipGetLastError(); return ZKWG_RC_OOM; }
+          B.drop(work);
+          work = B.get(zkwg_msm_work_bytes(plan.p));
+          if (B.oom) return ZKWG_RC_OOM;
           work_for = m;
         }
         u8 part[128];
-        rc = group == 1 ? zkwg_msm_g1_device(B.plan, s, 0, 0, B.work, part, st) : zkwg_msm_g2_device(B.plan, s, 0, 0, B.work, part, st);
-        zkwg_msm_destroy(B.plan); B.plan = nullptr;
+        rc = group == 1 ? zkwg_msm_g1_device(plan.p, s, 0, 0, work, part, st) : zkwg_msm_g2_device(plan.p, s, 0, 0, work, part, st);
+        zkwg_msm_destroy(plan.p); plan.p = nullptr;
         if (rc != ZKWG_RC_OK) return rc;
         (which ? sb : sa).add(group, part);
       }
@@ -110,23 +102,25 @@ int zkwg_pairing_check(const uint8_t* g1, const uint8_t* g2, uint32_t n, int* is
 #endif
 
 int zkwg_g2_subgroup_device(int device, const void* d_points, uint64_t n, uint64_t* n_bad, uint64_t* first_bad, void* hip_stream) {
-  if (!n_bad || !first_bad || (n && !d_points) || ((uintptr_t)d_points & 15)) return ZKWG_RC_BAD_ARG;
+  if (!n_bad || !first_bad || zk_bad_point_args(2, d_points, n, d_points)) return ZKWG_RC_BAD_ARG;
   if (device < 0) return ZKWG_RC_NO_DEVICE;
   if (hipSetDevice(device) != hipSuccess) return ZKWG_RC_HIP_ERROR;
   *n_bad = 0;
   if (!n) return ZKWG_RC_OK;
   hipStream_t st = (hipStream_t)hip_stream;
-  Buffers B;
-  if (hipMalloc(&B.tab, std::min<u64>(n, ZK_VERIFY_PIECE) * 128) != hipSuccess || hipMalloc((void**)&B.flags, 12) != hipSuccess) { (void)hipGetLastError(); return ZKWG_RC_OOM; }
+  DevBufs B;
+  void* tab = B.get(std::min<u64>(n, ZK_VERIFY_PIECE) * 128);
+  u32* d_flags = (u32*)B.get(12);
+  if (B.oom) return ZKWG_RC_OOM;
   const ZkPhase2Digits Du = zk_verify_u_digits();
   bool found = false;
   for (u64 at = 0; at < n; at += ZK_VERIFY_PIECE) {
     const u32 m = (u32)std::min<u64>(ZK_VERIFY_PIECE, n - at);
     u32 flags[3] = {0, 0, 0xffffffffu};                          // off the curve | outside the subgroup | the lowest index of one
-    if (hipMemcpyAsync(B.flags, flags, 12, hipMemcpyHostToDevice, st) != hipSuccess) return ZKWG_RC_HIP_ERROR;
-    zk_setup_prepare_launch(2, (const u8*)d_points + at * 128, B.tab, m, B.flags, st);      // the curve check; -> the tables' form
-    zk_verify_g2_subgroup_launch(B.tab, m, Du, B.flags + 1, st);
-    if (hipGetLastError() != hipSuccess || hipMemcpyAsync(flags, B.flags, 12, hipMemcpyDeviceToHost, st) != hipSuccess || hipStreamSynchronize(st) != hipSuccess) return ZKWG_RC_HIP_ERROR;
+    if (hipMemcpyAsync(d_flags, flags, 12, hipMemcpyHostToDevice, st) != hipSuccess) return ZKWG_RC_HIP_ERROR;
+    zk_setup_prepare_launch(2, (const u8*)d_points + at * 128, tab, m, d_flags, st);        // the curve check; -> the tables' form
+    zk_verify_g2_subgroup_launch(tab, m, Du, d_flags + 1, st);
+    if (zk_read_flags(st, d_flags, flags, 3) != ZKWG_RC_OK) return ZKWG_RC_HIP_ERROR;
     if (flags[0]) return fail(NOT_ON_CURVE);
     if (flags[1] && !found) { *first_bad = at + flags[2]; found = true; }
     *n_bad += flags[1];

@@ -5,6 +5,7 @@ millions of points in front of a check are folded into its four points on the de
 Points are bytes in the zkey's form: G1 64 bytes, G2 128 bytes, little-endian Montgomery words, zeros = infinity."""
 import ctypes as C
 
+from . import _call
 from .zkey import Q
 
 
@@ -21,10 +22,7 @@ def check(pairs):
     if len(g1) != 64 * len(pairs) or len(g2) != 128 * len(pairs):
         raise PairingError("a G1 point is 64 bytes and a G2 point 128")
     one = C.c_int(0)
-    rc = lib.zkwg_pairing_check(g1, g2, len(pairs), C.byref(one))
-    if rc != 0:
-        msg = lib.zkwg_last_error().decode() if rc == -1 else ""
-        raise PairingError(f"{lib.zkwg_strerror(rc).decode()}{': ' + msg if msg else ''}")
+    _call.check(lib, lib.zkwg_pairing_check(g1, g2, len(pairs), C.byref(one)), PairingError)
     return bool(one.value)
 
 

@@ -39,7 +39,7 @@ import os
 import struct
 import sys
 
-from . import _lib, zkey
+from . import _call, _lib, zkey
 
 R, Q = zkey.R, zkey.Q
 COFACTOR_G2 = 2 * Q - R
@@ -52,11 +52,6 @@ TYPE_BEACON = 1
 
 class Phase2Error(ValueError):
     pass
-
-
-def _fail(lib, rc):
-    msg = lib.zkwg_last_error().decode() if rc == -1 else ""
-    raise Phase2Error(f"{lib.zkwg_strerror(rc).decode()}{': ' + msg if msg else ''}")
 
 
 def derive_scalar(seed_bytes, tag=TAG_SCALAR):
@@ -173,32 +168,20 @@ def scale_points(group, points, scalar, device=0):
         raise Phase2Error("points must be whole and the scalar below 2^256")
     if not points:
         return b""
-    dev = torch.device("cuda", device)
-    d = torch.frombuffer(bytearray(points), dtype=torch.uint8).to(dev)
+    d = _call.upload(points, device)
     out = torch.empty_like(d)
-    rc = lib.zkwg_point_scale_device(device, group, d.data_ptr(), len(points) // pt, int(scalar).to_bytes(32, "little"), out.data_ptr(), 0)
-    if rc != 0:
-        _fail(lib, rc)
-    return bytes(out.cpu().numpy())
+    _call.check(lib, lib.zkwg_point_scale_device(device, group, d.data_ptr(), len(points) // pt, _call.le32(scalar), out.data_ptr(), 0), Phase2Error)
+    return _call.download(out)
 
 
 def apply_delta(zkey_bytes, k, section10, device=0):
     """the key with delta times k and `section10` as its section 10 (zkwg_zkey_apply_delta) -> bytes"""
-    import numpy as np
     lib = _lib.load()
-    a = np.frombuffer(zkey_bytes, dtype=np.uint8)      # (no copy; works for an mmap)
-    size, out_len = C.c_uint64(), C.c_uint64()
-    try:
-        rc = lib.zkwg_zkey_apply_delta_size(a.ctypes.data, a.size, len(section10), C.byref(size))
-        if rc == 0:
-            out = (C.c_uint8 * size.value)()
-            rc = lib.zkwg_zkey_apply_delta(device, a.ctypes.data, a.size, int(k % (1 << 256)).to_bytes(32, "little"), bytes(section10), len(section10), out, size.value,
-                                           C.byref(out_len))
-    finally:
-        del a                                          # (an mmap cannot be closed while a view of it lives, e.g. in a traceback)
-    if rc != 0:
-        _fail(lib, rc)
-    return bytes(memoryview(out)[:out_len.value])
+    rc, out = _call.sized_call(lambda p, n, size: lib.zkwg_zkey_apply_delta_size(p, n, len(section10), size),
+                               lambda p, n, o, cap, out_len: lib.zkwg_zkey_apply_delta(device, p, n, _call.le32(k), bytes(section10), len(section10), o, cap, out_len),
+                               zkey_bytes)
+    _call.check(lib, rc, Phase2Error)
+    return out
 
 
 def last_stats():
@@ -244,10 +227,6 @@ def _f2_sqrt(a):
 _B2 = _f2_mul((3, 0), (9 * pow(82, -1, Q) % Q, -pow(82, -1, Q) % Q))      # 3 / (9 + i) = 3 (9 - i) / 82
 
 
-def _mont(v):
-    return ((v << 256) % Q).to_bytes(32, "little")
-
-
 def challenge_g2(transcript, device=0):
     """-> a point of G2 (128 bytes in the zkey's form) that only the transcript determines"""
     for counter in range(1 << 16):
@@ -258,7 +237,7 @@ def challenge_g2(transcript, device=0):
         if y is None:
             continue
         y = min(y, ((-y[0]) % Q, (-y[1]) % Q))       # (which root: the smaller pair)
-        p = scale_points(2, _mont(x[0]) + _mont(x[1]) + _mont(y[0]) + _mont(y[1]), COFACTOR_G2, device)
+        p = scale_points(2, b"".join(_call.mont(v) for v in x + y), COFACTOR_G2, device)
         if any(p):
             return p
     raise Phase2Error("no challenge point found")
@@ -329,8 +308,7 @@ def _zkey_check(data):
         rc = lib.zkwg_zkey_check(a.ctypes.data, a.size, None, None, None)
     finally:
         del a
-    if rc != 0:
-        _fail(lib, rc)
+    _call.check(lib, rc, Phase2Error)
 
 
 def _verify_record(rec, circuit_hash, earlier, before, device):

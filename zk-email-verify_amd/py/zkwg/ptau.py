@@ -55,6 +55,7 @@ import os
 import struct
 import sys
 
+from . import _call
 from .zkey import Q, R
 
 # (section id, bytes per point, points as a function of n = 2^power)
@@ -167,22 +168,12 @@ def truncate(data, power):
 def prepare(data, power=None, device=0):
     """an unprepared file (bytes, or an mmap: only the prefixes are read) -> the prepared file of `power` (None: the file's own) as
     bytes, sections 12 - 15 computed on the device (zkwg_ptau_prepare)"""
-    import numpy as np
     from . import _lib
     lib = _lib.load()
-    a = np.frombuffer(data, dtype=np.uint8)            # (no copy; works for an mmap)
-    size, out_len = C.c_uint64(), C.c_uint64()
-    try:
-        rc = lib.zkwg_ptau_prepare_size(a.ctypes.data, a.size, power or 0, C.byref(size))
-        if rc == 0:
-            out = np.empty(size.value, dtype=np.uint8)
-            rc = lib.zkwg_ptau_prepare(device, a.ctypes.data, a.size, power or 0, out.ctypes.data, size.value, C.byref(out_len))
-    finally:
-        del a                                          # (an mmap cannot be closed while a view of it lives)
-    if rc != 0:
-        msg = lib.zkwg_last_error().decode() if rc == -1 else ""
-        raise PtauError(f"{lib.zkwg_strerror(rc).decode()}{': ' + msg if msg else ''}")
-    return out[:out_len.value].tobytes()
+    rc, out = _call.sized_call(lambda p, n, size: lib.zkwg_ptau_prepare_size(p, n, power or 0, size),
+                               lambda p, n, o, cap, out_len: lib.zkwg_ptau_prepare(device, p, n, power or 0, o, cap, out_len), data)
+    _call.check(lib, rc, PtauError)
+    return out
 
 
 # ---- new / contribute / beacon --------------------------------------------------------------------------------------------------------------
@@ -197,13 +188,9 @@ _G2_GENERATOR = (0x1800deef121f1e76426a00665e5c4479674322d4f75edadd46debd5cd992f
                  0x12c85ea5db8c6deb4aab71808dcb408fe3d1e7690c43d37b4ce6cc0166fa7daa, 0x090689d0585ff075ec9e99ad690c3395bc4b313370b38ef355acdadcd122975b)
 
 
-def _mont(v):
-    return ((v << 256) % Q).to_bytes(32, "little")
-
-
 def generators():
     """-> (G1, G2) in the zkey's form: (1, 2) and the EIP-197 generator, the bases of zkwg_fixed_base_device"""
-    return _mont(1) + _mont(2), b"".join(_mont(v) for v in _G2_GENERATOR)
+    return _call.mont(1) + _call.mont(2), b"".join(_call.mont(v) for v in _G2_GENERATOR)
 
 
 def new(power):
@@ -212,18 +199,6 @@ def new(power):
         raise PtauError(".ptau: power out of range")
     n, (g1, g2) = 1 << power, generators()
     return write_ptau(power, {2: g1 * (2 * n - 1), 3: g2 * n, 4: g1 * n, 5: g1 * n, 6: g2})
-
-
-BAD_CONFIG = -1                                   # ZKWG_RC_BAD_CONFIG: the one code zkwg_last_error has a message for
-
-
-def _fail(lib, rc):
-    msg = lib.zkwg_last_error().decode() if rc == BAD_CONFIG else ""
-    raise PtauError(f"{lib.zkwg_strerror(rc).decode()}{': ' + msg if msg else ''}")
-
-
-def _le32(v):
-    return int(v % (1 << 256)).to_bytes(32, "little")
 
 
 def point_mul(group, points, scalars, device=0):
@@ -236,14 +211,10 @@ def point_mul(group, points, scalars, device=0):
         raise PtauError("one scalar per whole point")
     if not scalars:
         return b""
-    dev = torch.device("cuda", device)
-    d = torch.frombuffer(bytearray(points), dtype=torch.uint8).to(dev)
-    k = torch.frombuffer(bytearray(b"".join(_le32(s) for s in scalars)), dtype=torch.uint8).to(dev)
+    d, k = _call.upload(points, device), _call.upload(b"".join(_call.le32(s) for s in scalars), device)
     out = torch.empty_like(d)
-    rc = lib.zkwg_point_mul_device(device, group, d.data_ptr(), len(scalars), k.data_ptr(), out.data_ptr(), 0)
-    if rc != 0:
-        _fail(lib, rc)
-    return bytes(out.cpu().numpy())
+    _call.check(lib, lib.zkwg_point_mul_device(device, group, d.data_ptr(), len(scalars), k.data_ptr(), out.data_ptr(), 0), PtauError)
+    return _call.download(out)
 
 
 def point_powers(group, points, c, t, first=0, device=0):
@@ -256,33 +227,21 @@ def point_powers(group, points, c, t, first=0, device=0):
         raise PtauError("the points must be whole")
     if not points:
         return b""
-    dev = torch.device("cuda", device)
-    d = torch.frombuffer(bytearray(points), dtype=torch.uint8).to(dev)
+    d = _call.upload(points, device)
     out = torch.empty_like(d)
-    rc = lib.zkwg_point_powers_device(device, group, d.data_ptr(), len(points) // pt, _le32(c), _le32(t), first, out.data_ptr(), 0)
-    if rc != 0:
-        _fail(lib, rc)
-    return bytes(out.cpu().numpy())
+    _call.check(lib, lib.zkwg_point_powers_device(device, group, d.data_ptr(), len(points) // pt, _call.le32(c), _call.le32(t), first, out.data_ptr(), 0), PtauError)
+    return _call.download(out)
 
 
 def apply_key(data, tau, alpha, beta, section7, device=0):
     """the unprepared file after the contribution (tau, alpha, beta), with `section7` as its section 7 (zkwg_ptau_apply_key) -> bytes"""
-    import numpy as np
     from . import _lib
     lib = _lib.load()
-    a = np.frombuffer(data, dtype=np.uint8)            # (no copy; works for an mmap)
-    size, out_len = C.c_uint64(), C.c_uint64()
-    try:
-        rc = lib.zkwg_ptau_apply_key_size(a.ctypes.data, a.size, len(section7), C.byref(size))
-        if rc == 0:
-            out = np.empty(size.value, dtype=np.uint8)
-            rc = lib.zkwg_ptau_apply_key(device, a.ctypes.data, a.size, _le32(tau), _le32(alpha), _le32(beta), bytes(section7), len(section7),
-                                         out.ctypes.data, size.value, C.byref(out_len))
-    finally:
-        del a                                          # (an mmap cannot be closed while a view of it lives)
-    if rc != 0:
-        _fail(lib, rc)
-    return out[:out_len.value].tobytes()
+    keys = [_call.le32(v) for v in (tau, alpha, beta)]
+    rc, out = _call.sized_call(lambda p, n, size: lib.zkwg_ptau_apply_key_size(p, n, len(section7), size),
+                               lambda p, n, o, cap, out_len: lib.zkwg_ptau_apply_key(device, p, n, *keys, bytes(section7), len(section7), o, cap, out_len), data)
+    _call.check(lib, rc, PtauError)
+    return out
 
 
 def apply_key_stats():
@@ -437,19 +396,15 @@ def last_stats():
 
 def group_ntt(group, points, inverse, device=0):
     """the Fourier transform over `points` (bytes in the zkey's form, a power of two of them) -> bytes (zkwg_group_ntt_device)"""
-    import torch
     from . import _lib
     lib = _lib.load()
     pt = 64 if group == 1 else 128
     n = len(points) // pt
     if n * pt != len(points) or n == 0 or n & (n - 1):
         raise PtauError("the points must be whole and a power of two of them")
-    d = torch.frombuffer(bytearray(points), dtype=torch.uint8).to(torch.device("cuda", device))
-    rc = lib.zkwg_group_ntt_device(device, group, d.data_ptr(), n.bit_length() - 1, 1 if inverse else 0, 0)
-    if rc != 0:
-        msg = lib.zkwg_last_error().decode() if rc == -1 else ""
-        raise PtauError(f"{lib.zkwg_strerror(rc).decode()}{': ' + msg if msg else ''}")
-    return bytes(d.cpu().numpy())
+    d = _call.upload(points, device)
+    _call.check(lib, lib.zkwg_group_ntt_device(device, group, d.data_ptr(), n.bit_length() - 1, 1 if inverse else 0, 0), PtauError)
+    return _call.download(d)
 
 
 # ---- verify ---------------------------------------------------------------------------------------------------------------------------------------
@@ -469,14 +424,12 @@ class _Device:
         self.dev = torch.device("cuda", device)
 
     def upload(self, data):
-        return self.torch.frombuffer(bytearray(data), dtype=self.torch.uint8).to(self.dev)
+        return _call.upload(data, self.device)
 
     def g2_subgroup(self, points, n):
         """-> (points outside the subgroup, the lowest index of one or None)"""
         n_bad, first = C.c_uint64(), C.c_uint64()
-        rc = self.lib.zkwg_g2_subgroup_device(self.device, points.data_ptr(), n, C.byref(n_bad), C.byref(first), 0)
-        if rc != 0:
-            _fail(self.lib, rc)
+        _call.check(self.lib, self.lib.zkwg_g2_subgroup_device(self.device, points.data_ptr(), n, C.byref(n_bad), C.byref(first), 0), PtauError)
         return n_bad.value, (first.value if n_bad.value else None)
 
     def rlc(self, group, points, first, n, scalars, wide=False, shifted=False, piece=0, other=None):
@@ -489,10 +442,9 @@ class _Device:
         out_a, out_b = (C.c_uint8 * pt)(), (C.c_uint8 * pt)()
         fn = self.lib.zkwg_point_rlc32_device if wide else self.lib.zkwg_point_rlc_device
         rc = fn(self.device, group, a, b, n, scalars.data_ptr(), piece, out_a, out_b if b is not None else None, 0)
-        if rc == BAD_CONFIG:
+        if rc == _call.BAD_CONFIG:
             raise PointRefused(f"{self.lib.zkwg_strerror(rc).decode()}: {self.lib.zkwg_last_error().decode()}")
-        if rc != 0:
-            _fail(self.lib, rc)
+        _call.check(self.lib, rc, PtauError)
         return bytes(out_a), (bytes(out_b) if b is not None else None)
 
     def ifft(self, scalars16, q):
@@ -508,8 +460,7 @@ class _Device:
             # (the transform is linear and its tables carry the Montgomery factor: standard-form values in, standard-form values out)
             rc = self.lib.zkwg_ntt_transform_device(plan, d.data_ptr(), 1, 1, 0)
             self.lib.zkwg_ntt_destroy(plan)
-        if rc != 0:
-            _fail(self.lib, rc)
+        _call.check(self.lib, rc, PtauError)
         return d
 
 

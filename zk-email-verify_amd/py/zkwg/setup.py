@@ -9,18 +9,13 @@ import json
 import mmap
 import sys
 
-from . import _lib
+from . import _call, _lib
 
 SLICE_NAMES = ("tau_g1", "tau_g2", "alpha_tau_g1", "beta_tau_g1", "tau_g1_next")
 
 
 class SetupError(ValueError):
     pass
-
-
-def _fail(lib, rc):
-    msg = lib.zkwg_last_error().decode() if rc == -1 else ""
-    raise SetupError(f"{lib.zkwg_strerror(rc).decode()}{': ' + msg if msg else ''}")
 
 
 def _host_ptr(buf, keep):
@@ -34,9 +29,7 @@ def key_shape(r1cs_bytes):
     """-> (domain power, bytes of the .zkey) of a compiler-format .r1cs"""
     lib = _lib.load()
     power, size = C.c_uint32(), C.c_uint64()
-    rc = lib.zkwg_zkey_new_size(r1cs_bytes, len(r1cs_bytes), C.byref(power), C.byref(size))
-    if rc != 0:
-        _fail(lib, rc)
+    _call.check(lib, lib.zkwg_zkey_new_size(r1cs_bytes, len(r1cs_bytes), C.byref(power), C.byref(size)), SetupError)
     return power.value, size.value
 
 
@@ -71,14 +64,10 @@ def new_zkey(r1cs_bytes, ptau_or_slices, device=0):
             C.memmove(getattr(sl, k), bytes(d[k]), n)
     else:
         ptr, n = _host_ptr(ptau_or_slices, keep)
-        rc = lib.zkwg_ptau_parse(ptr, n, power, C.byref(sl))
-        if rc != 0:
-            _fail(lib, rc)
+        _call.check(lib, lib.zkwg_ptau_parse(ptr, n, power, C.byref(sl)), SetupError)
     out = (C.c_uint8 * size)()
     out_len = C.c_uint64()
-    rc = lib.zkwg_zkey_new(device, r1cs_bytes, len(r1cs_bytes), C.byref(sl), out, size, C.byref(out_len))
-    if rc != 0:
-        _fail(lib, rc)
+    _call.check(lib, lib.zkwg_zkey_new(device, r1cs_bytes, len(r1cs_bytes), C.byref(sl), out, size, C.byref(out_len)), SetupError)
     return bytes(memoryview(out)[:out_len.value])
 
 
