@@ -766,6 +766,47 @@ int zkwg_point_rlc_device(int device, int group, const void* d_a, const void* d_
 int zkwg_point_rlc32_device(int device, int group, const void* d_a, const void* d_b, uint64_t n, const void* d_scalars, uint64_t piece_points,
                             uint8_t* out_a, uint8_t* out_b, void* hip_stream);
 
+/* ---- checking proofs: batched groth16 verification (csrc/zkwg_pair_core.h, csrc/zkwg_pair_host.h) ----------------------
+ * `snarkjs groth16 verify` (reference: packages/helpers/src/chunked-zkey.ts:93-101) for MANY proofs of one key.  With random 128-bit
+ * r_i the proofs of a batch are all valid, up to an error of about 2^-128 per batch, iff
+ *     FE( prod_i f(r_i A_i, B_i) . f(-S0 alpha, beta) . f(-V, gamma) . f(-Cs, delta) ) = 1,
+ *     S0 = sum r_i,  V = S0 IC_0 + sum_j (sum_i r_i x_ij) IC_j,  Cs = sum_i r_i C_i     (f: the Miller function, FE: the final exponentiation).
+ * The device runs what grows with the batch -- one Miller loop per proof on a lane pair, the subgroup test of its B_i, the scalings
+ * r_i A_i and r_i C_i, the product tree; the host adds three Miller loops and ONE final exponentiation per check.  When the batch
+ * check fails the host bisects over the per-proof values (downloaded once, the same r_i): with k bad proofs among n at most
+ * min(2 n - 1, 1 + 2 k ceil(log2 n)) checks.  A batch of mostly bad proofs is slow by design.
+ *
+ * zkwg_miller_device: f[i] = Miller value of (g1[i], g2[i]) up to a factor in Fq2 (the final exponentiation removes it: FE(f[i]) is the
+ * reduced pairing); inside[i] = g2[i] in the subgroup of order r (f[i] means nothing when it is not).  Device pointers, the zkey's point form
+ * (zeros = infinity -> f = 1, inside = 1), 16-byte aligned; f: n x 384 bytes, six Fq2 of w^0 .. w^5 (w^6 = 9 + i) as Montgomery words.
+ * Every point is curve-checked first; one that fails refuses the call ("curve").  n <= 2^20.
+ * zkwg_fq12_product_device: out (384 bytes, host memory) = the product of the f[i] with use[i] != 0 (d_use NULL: all of them; none: 1),
+ * as a tree of launches; exact, so the result does not depend on the tree.
+ *
+ * zkwg_groth16_verify_batch: ok[i] = 1 iff proof i verifies.  proofs: n x 256 bytes in the form zkwg_prover_prove_* writes (standard-form
+ * little-endian integers); publics: n x n_public x 32 bytes, little-endian standard form; rand16: n x 16 bytes, every entry non-zero (a
+ * zero entry: ZKWG_RC_BAD_ARG), or NULL = drawn from the operating system inside the call.  device >= 0: Miller loops, subgroup tests
+ * and the per-proof scalings on that device; device = -1: the same algorithm on the host alone (zkwg_pairing.h) -- the yardstick and
+ * what a machine without a GPU runs.  n <= 2^20.  ok[i] = 0 without refusing the call: a public input >= r, a coordinate >= q, A, B or
+ * C off its curve or all zeros (infinity: what the prover writes for a failed email), B outside the subgroup of order r -- outside it
+ * the pairing is not bilinear and the batch equation means nothing (snarkjs does not test this; arkworks does when it deserialises).
+ * The key is checked once per call (every point reduced, on its curve, not infinity; beta2, gamma2, delta2 in the subgroup); a bad key is
+ * refused with ZKWG_RC_BAD_CONFIG + zkwg_last_error ("curve" / "subgroup"), never turned into verdicts.  n = 0 is ZKWG_RC_OK.
+ * Device memory: 1,001 bytes per proof beside what zkwg_point_mul_device takes while it runs (2,024), freed before the call returns.
+ * zkwg_groth16_verify_stats, of this thread's last call: seconds = {host checks + upload, scalings, Miller + subgroup, product +
+ * download, host pairing of the batch check, bisection}; counts = {pairs sent to the device (or made on the host), host final
+ * exponentiations, proofs excluded before the device, proofs found bad after that (subgroup flag or bisection)}. */
+int zkwg_miller_device(int device, const void* d_g1, const void* d_g2, uint64_t n, void* d_f, uint8_t* d_inside, void* hip_stream);
+int zkwg_fq12_product_device(int device, const void* d_f, const uint8_t* d_use, uint64_t n, uint8_t* out, void* hip_stream);
+typedef struct zkwg_verification_key {
+  uint32_t n_public;
+  uint8_t alpha1[64], beta2[128], gamma2[128], delta2[128];   /* as a zkey's header stores them */
+  const uint8_t* ic;                                          /* (n_public + 1) x 64 bytes, the same form */
+} zkwg_verification_key;
+int zkwg_groth16_verify_batch(int device, const zkwg_verification_key* vk, uint64_t n, const uint8_t* proofs,
+                              const uint8_t* publics, const uint8_t* rand16, uint8_t* ok);
+void zkwg_groth16_verify_stats(double seconds[6], uint64_t counts[4]);
+
 /* ---- the compact image as a device-side interchange format --------------------------
  * zkwg_prepare_device leaves, per email, a compact IMAGE in the scratch buffer (~0.45 MB instead of the 57 MB
  * witness of EmailVerifier(1024,1536)): `bits` (u64 words of LSB-first bit groups), `small` (u32 values) and
