@@ -401,11 +401,11 @@ void ht_msm_device_mirror_batch(int group, const uint8_t* points, const uint64_t
 void ht_msm_device_mirror(const uint8_t* points, const uint64_t* scalars, uint64_t n, uint32_t c, int mont, uint32_t shuffle, int layout, uint8_t* out) {
   ht_msm_device_mirror_batch(1, points, scalars, n, 1, c, mont, shuffle, layout, 16, out);
 }
-unsigned long long ht_fq29_violations() { return zk_fq29_violations; }
+unsigned long long ht_fq29_violations() { return zk_fq29_all_violations(); }
 
 // The lazy-limb point arithmetic by itself (zkwg_ec29.h), standard form across this boundary.  op 0: scaled(a) + b mixed; 1: scaled(a) +
 // scaled(b); 2: 2 a (affine); 3: 2 scaled(a); `reps` > 1 repeats op 0 / 1 / 3 on the running result (accumulated bounds: acc = acc + b ...)
-static Fq29 ht_q29(const Fq& canon_r256) { return fq29_from_fq(zk_fq_r256_to_r261(canon_r256)); }
+static Fq29 ht_q29(const Fq& canon_r256) { return zk_q29_base(zk_fq_r256_to_r261(canon_r256)); }          // [1, 1]: fq29_to_fq reduced it below q
 void ht_ec29_g1_op(int op, const uint8_t* a, const uint8_t* b, const uint8_t* scale, uint32_t reps, uint8_t* out) {
   typedef ZkF1 F;
   const G1Affine A = ht_pt_in(a), B = ht_pt_in(b);
@@ -466,6 +466,47 @@ void ht_fq29_op(int op, const uint8_t* a, const uint8_t* b, const uint8_t* c, co
   const Fq m = fq29_to_fq<16>(fq29_mul(r, fq29_r256()));
   const Fq st = fq_from_mont(m);
   memcpy(out, &st, 32);
+}
+}
+
+// The bound checker of zkwg_fq29.h itself (tests/test_fq29_bounds_cpu.py): raw limb-form operands with CLAIMED bounds, so that a test can put
+// the actual values anywhere below them -- at the top of a contract, or far below bounds that break a rule.
+extern "C" {
+// the three counters: preconditions violated by the values, by the bounds, results above their own bounds
+void ht_fq29_counters(unsigned long long* out) { out[0] = zk_fq29_violations; out[1] = zk_fq29_bound_violations; out[2] = zk_fq29_bound_unsound; }
+// puts the counters back (the test that raises the bound counter on purpose leaves the library as it found it)
+void ht_fq29_counters_set(const unsigned long long* in) { zk_fq29_violations = in[0]; zk_fq29_bound_violations = in[1]; zk_fq29_bound_unsound = in[2]; }
+// limbs: 4 operands x 9 limbs; claims: 4 x (U, V) (U = 0: no claim -- the limbs are their own bounds).  op 0 mul(a, b), 1 sqr(a), 2 dot2(a, b, c, d),
+// 3 add(a, b), 4 norm(a), 5 .. 9 sub<2, 1>, <3, 1>, <5, 2>, <12, 1>, <8, 1>(a, b), 10 .. 12 to_fq<2>, <3>, <16>(a) (the canonical words, split again),
+// 13 a + a + ... (`reps` copies) then norm, 14 is_zero_mod<5>(a), 15 maybe_zero<14>(a) (out[0] = the verdict).  out: the result's 9 limbs; sh: its
+// limb bounds (9) and its value bound in units of q / 2^20
+void ht_fq29_bound_op(int op, uint32_t reps, const uint32_t* limbs, const uint32_t* claims, uint32_t* out, unsigned long long* sh) {
+  Fq29 v[4];
+  for (int k = 0; k < 4; ++k) {
+    for (int i = 0; i < 9; ++i) v[k].l[i] = limbs[9 * k + i];
+    if (claims[2 * k]) ZKQ29_ASSUME(v[k], claims[2 * k], claims[2 * k + 1]);          // the test states the bounds it wants checked
+  }
+  const Fq29 &a = v[0], &b = v[1], &c = v[2], &d = v[3];
+  Fq29 r = fq29_zero();
+  if (op == 0) r = fq29_mul(a, b);
+  else if (op == 1) r = fq29_sqr(a);
+  else if (op == 2) r = fq29_dot2(a, b, c, d);
+  else if (op == 3) r = fq29_add(a, b);
+  else if (op == 4) r = fq29_norm(a);
+  else if (op == 5) r = fq29_sub<2, 1>(a, b);
+  else if (op == 6) r = fq29_sub<3, 1>(a, b);
+  else if (op == 7) r = fq29_sub<5, 2>(a, b);
+  else if (op == 8) r = fq29_sub<12, 1>(a, b);
+  else if (op == 9) r = fq29_sub<8, 1>(a, b);
+  else if (op == 10) r = fq29_from_fq(fq29_to_fq<2>(a));
+  else if (op == 11) r = fq29_from_fq(fq29_to_fq<3>(a));
+  else if (op == 12) r = fq29_from_fq(fq29_to_fq<16>(a));
+  else if (op == 13) { r = a; for (uint32_t i = 1; i < reps; ++i) r = fq29_add(r, a); r = fq29_norm(r); }
+  else if (op == 14) r.l[0] = fq29_is_zero_mod<5>(a) ? 1u : 0u;
+  else r.l[0] = fq29_maybe_zero<14>(a) ? 1u : 0u;
+  const ZkQ29Sh s = zk_q29_sh(r);
+  for (int i = 0; i < 9; ++i) { out[i] = r.l[i]; sh[i] = s.ub[i]; }
+  sh[9] = s.vb;
 }
 }
 

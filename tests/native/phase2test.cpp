@@ -5,7 +5,7 @@
 #include "zkwg_phase2_core.h"
 
 extern "C" {
-unsigned long long p2_violations() { return zk_fq29_violations; }
+unsigned long long p2_violations() { return zk_fq29_all_violations(); }
 // scalar (32 bytes, little-endian) -> nz[9] | neg[9] | len | n_nz
 void p2_recode(const u8* scalar, u32* out) {
   const ZkPhase2Digits D = zk_phase2_recode(scalar);

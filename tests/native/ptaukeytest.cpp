@@ -10,7 +10,7 @@ static void pk_err(const std::string& e, char* err, u64 cap) {
 }
 
 extern "C" {
-unsigned long long pk_violations() { return zk_fq29_violations + zk_fr29_violations; }
+unsigned long long pk_violations() { return zk_fq29_all_violations() + zk_fr29_violations; }
 u32 pk_window() { return ZK_KEY_W; }
 // k (32 bytes, below r) -> out[0 .. 64): the digits from the LEAST significant window up, as the walk reads them; out[64]: 1 when P is subtracted
 void pk_recode(const u8* k32, int* out) {

@@ -9,7 +9,7 @@ static void pt_err(const std::string& e, char* err, u64 cap) {
 }
 
 extern "C" {
-unsigned long long pt_violations() { return zk_fq29_violations; }
+unsigned long long pt_violations() { return zk_fq29_all_violations(); }
 // the table of a 2^L-point transform: out = 2^(L - 1) entries of nz[8] | neg[8] (one entry for L = 0)
 void pt_table(u32 L, int inverse, u32* out) {
   ZkPtauTable T;

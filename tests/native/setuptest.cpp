@@ -9,7 +9,7 @@ static void st_err(const std::string& e, char* err, u64 cap) {
 }
 
 extern "C" {
-unsigned long long st_violations() { return zk_fq29_violations; }
+unsigned long long st_violations() { return zk_fq29_all_violations(); }
 // offsets[5]: tau_g1, tau_g2, alpha_tau_g1, beta_tau_g1, tau_g1_next as offsets into the file; points: alpha1 | beta1 | beta2
 int st_ptau_parse(const u8* p, u64 len, u32 power, u64* offsets, u8* points, char* err, u64 err_cap) {
   zkwg_setup_slices S;

@@ -9,7 +9,7 @@ static void vt_err(const std::string& e, char* err, u64 cap) {
 }
 
 extern "C" {
-unsigned long long vt_violations() { return zk_fq29_violations; }
+unsigned long long vt_violations() { return zk_fq29_all_violations(); }
 // the digits of u: positions and non-zero digits of the shared walk
 void vt_u_digits(u32* len, u32* n_nz) { const ZkPhase2Digits D = zk_verify_u_digits(); *len = D.len; *n_nz = D.n_nz; }
 // inside[i] = 1 when point i (the zkey's form) is in the subgroup of order r; 0, or -1 when a point is not on the curve

@@ -23,6 +23,12 @@ def load():
     lib.pt_final_exp.argtypes = [C.c_char_p, vp]
     lib.pt_f12_mul.restype = None
     lib.pt_f12_mul.argtypes = [C.c_char_p, C.c_char_p, C.c_int, vp]
+    lib.pt_pair_product.restype = None
+    lib.pt_pair_product.argtypes = [C.c_char_p, C.c_char_p, u32, vp]
+    lib.pt_pair_piece.restype = None
+    lib.pt_pair_piece.argtypes = [C.c_int, C.c_char_p, vp]
+    lib.pt_counters.restype = None
+    lib.pt_counters.argtypes = [vp]
     lib.pt_verify_batch.restype = C.c_int
     lib.pt_verify_batch.argtypes = [C.c_char_p, C.c_char_p, u32, u64, C.c_char_p, C.c_char_p, C.c_char_p, vp, vp, vp, C.c_char_p, u64]
     return lib
@@ -58,6 +64,47 @@ def f12_mul(a, b, core=False):
     out = (C.c_uint8 * 384)()
     load().pt_f12_mul(a, b, 1 if core else 0, out)
     return bytes(out)
+
+
+def counters():
+    """(preconditions violated by the values, by the bounds, results above their own bounds) of csrc/zkwg_fq29.h in this library"""
+    out = (C.c_ulonglong * 3)()
+    load().pt_counters(out)
+    return tuple(out)
+
+
+def pair_product(values, use=None):
+    """one level of the product tree as zk_pair_product runs it: 384-byte values, flags or None -> ceil(n / 4) values"""
+    n = len(values)
+    out = (C.c_uint8 * (384 * ((n + 3) // 4)))()
+    load().pt_pair_product(b"".join(values), None if use is None else bytes(use), n, out)
+    return [bytes(out[384 * j:384 * j + 384]) for j in range((n + 3) // 4)]
+
+
+def pair_piece(op, words, n_out):
+    """one piece of the Miller loop (tests/native/pairtest.cpp pt_pair_piece) on standard-form integers below q -> n_out integers"""
+    out = (C.c_uint8 * (32 * n_out))()
+    load().pt_pair_piece(op, b"".join(int(w).to_bytes(32, "little") for w in words), out)
+    return [int.from_bytes(bytes(out[32 * i:32 * i + 32]), "little") for i in range(n_out)]
+
+
+def f12_to_oracle(b):
+    """the inverse of f12_from_oracle"""
+    rinv = pow(1 << 256, -1, Q)
+    v = [int.from_bytes(b[o:o + 32], "little") * rinv % Q for o in range(0, 384, 32)]
+    return tuple((v[2 * k], v[2 * k + 1]) for k in range(6))
+
+
+def f12_edge_family(seed):
+    """Fq12 values at the edges of the limb form, as 384 stored bytes (Montgomery words): every word q - 1; every word 2^232 - 1 (all
+    29-bit limbs of the split word are ones); every word 1; only c5 non-zero (the hi / xi path of a product alone); only c0 non-zero; and
+    two random elements -> [(name, bytes)]"""
+    import random
+    rng = random.Random(seed)
+    word = lambda v: int(v).to_bytes(32, "little")
+    rnd2 = lambda: word(rng.randrange(Q)) + word(rng.randrange(Q))
+    return [("q-1", word(Q - 1) * 12), ("2^232-1", word((1 << 232) - 1) * 12), ("1", word(1) * 12), ("c5", bytes(320) + rnd2()), ("c0", rnd2() + bytes(320)),
+            ("random", b"".join(rnd2() for _ in range(6))), ("random2", b"".join(rnd2() for _ in range(6)))]
 
 
 def f12_from_oracle(f):

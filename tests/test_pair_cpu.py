@@ -66,6 +66,36 @@ def test_bilinearity_of_the_core_miller_values(pairs):
     assert pairtest.f12_mul(f1, pairtest.ONE, True) == f1 == pairtest.f12_mul(pairtest.ONE, f1, True)
 
 
+def test_the_core_product_at_edge_words_equals_the_oracle_and_the_host():
+    """every stored word q - 1, every limb all ones, every word 1, c5 alone (the hi / xi path alone), c0 alone, each against itself, against
+    each other and against random elements: the expected product is oracle/pyref/bn254_pairing.f12_mul on Python integers"""
+    fam = pairtest.f12_edge_family(1340)
+    for na, a in fam:
+        for nb, b in fam:
+            want = pairtest.f12_from_oracle(P.f12_mul(pairtest.f12_to_oracle(a), pairtest.f12_to_oracle(b)))
+            assert pairtest.f12_mul(a, b, True) == want, (na, nb)
+            assert pairtest.f12_mul(a, b, False) == want, (na, nb)
+    assert pairtest.f12_to_oracle(pairtest.f12_from_oracle(P.F12_ONE)) == P.F12_ONE and pairtest.f12_from_oracle(P.F12_ONE) == pairtest.ONE
+    assert pairtest.violations() == 0
+
+
+def test_one_level_of_the_product_tree_as_the_kernel_folds_it_equals_the_oracle():
+    """the loop of zk_pair_product (csrc/zkwg_kernels_pair.hip) in the host build, its carried accumulator claimed after every product"""
+    fam = [v for _, v in pairtest.f12_edge_family(1341)]
+    vals = [fam[i % len(fam)] for i in range(17)]
+    for n in (1, 4, 5, 17):
+        for use in (None, [0 if i in (0, n // 2, n - 1) else 1 for i in range(n)]):
+            want = []
+            for j in range(0, n, 4):
+                acc = P.F12_ONE
+                for i in range(j, min(j + 4, n)):
+                    if use is None or use[i]:
+                        acc = P.f12_mul(acc, pairtest.f12_to_oracle(vals[i]))
+                want.append(pairtest.f12_from_oracle(acc))
+            assert pairtest.pair_product(vals[:n], use) == want, (n, use is None)
+    assert pairtest.violations() == 0
+
+
 def test_infinity_on_either_side_gives_exactly_one(pairs):
     _, pts = pairs
     p, q = pts[0]

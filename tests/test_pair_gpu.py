@@ -130,6 +130,31 @@ def test_the_product_tree_equals_the_host_product(leaves, n):
     torch.cuda.synchronize()
 
 
+@pytest.mark.parametrize("n", [1, 4, 5, 17])
+def test_the_product_tree_at_edge_words_equals_the_oracle(n):
+    """zkwg_fq12_product_device on values the Miller loop never makes -- every stored word q - 1, every 29-bit limb all ones, every word 1,
+    c5 alone, c0 alone, random elements -- for one value, exactly one lane pair's fold of 4, one past it, and two tree levels with a ragged
+    end; with every value in use and with the first, a middle and the last one switched off.  Expected: the product on Python integers
+    (oracle/pyref/bn254_pairing.f12_mul), not the host build of the kernel's header.  Exact."""
+    import torch
+    from oracle.pyref import bn254_pairing as P
+    from zkwg import _call, _lib
+    lib = _lib.load()
+    fam = [v for _, v in pairtest.f12_edge_family(1341)]
+    vals = [fam[i % len(fam)] for i in range(n)]
+    d_f = _call.upload(b"".join(vals), 0)
+    for use in (None, [0 if i in (0, n // 2, n - 1) else 1 for i in range(n)]):
+        d_use = None if use is None else _call.upload(bytes(use), 0)
+        out = (C.c_uint8 * 384)()
+        assert lib.zkwg_fq12_product_device(0, d_f.data_ptr(), None if use is None else d_use.data_ptr(), n, out, None) == 0
+        want = P.F12_ONE
+        for i in range(n):
+            if use is None or use[i]:
+                want = P.f12_mul(want, pairtest.f12_to_oracle(vals[i]))
+        assert bytes(out) == pairtest.f12_from_oracle(want), (n, use is None)
+    torch.cuda.synchronize()
+
+
 # ---- verdicts ---------------------------------------------------------------------------------------------------------------------------------
 @pytest.fixture(scope="module")
 def toy():

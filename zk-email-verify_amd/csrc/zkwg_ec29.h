@@ -14,8 +14,13 @@
 // Bounds (notation of zkwg_fq29.h: [U, V] = limbs < U 2^29, value < V q).  Stored accumulators: X = [1, 11], Y = [1, 7] (G1: [1, 2] --
 // Y3 = R (Q - X3) - Y1 PPP is ONE two-product dot product there, its result normalised), ZZ, ZZZ = [1, 2]; ZZ = 0 (all limbs) = infinity.
 // Bases: canonical words in 2^261-Montgomery form, [1, 1].  The bound of every intermediate is written beside it; `mul<VB>` names the
-// value bound of its RIGHT operand (G2's even lane needs a multiple of q above it to negate the partner's half); the host build counts
-// violated preconditions (ZKWG_FQ29_CHECK).
+// value bound of its RIGHT operand (G2's even lane needs a multiple of q above it to negate the partner's half: the negated half is
+// [2, VB + 1] whatever b is, so an Fq2 product is below (Va Vb + Va (VB + 1)) / 169.28 + 1 q, not Va Vb / 169 + 1).  The host check build
+// PROVES these comments (ZKWG_FQ29_CHECK, zkwg_fq29.h): every formula claims the Xyzz29 / Aff29 contract on its operands -- checked against
+// what the caller passed, then widened to exactly X [1, 11], Y [1, 7] (G1 [1, 2]), ZZ, ZZZ [1, 2], x [1, 1], y [2, 2] -- and on its result,
+// mul<VB> / sqr<VA> / msub<VB, VD> check the named operand against their argument (ZkF1 too), and every fq29_* operation checks its
+// preconditions on the BOUNDS: one call per branch is the formula for every input (tests/test_fq29_bounds_cpu.py, and every kernel core
+// the CPU tests run inherits it).  A base's coordinate is [1, 1] by assumption (zk_q29_base names what enforces it).
 #pragma once
 #include "zkwg_fq29.h"
 #include "zkwg_g1.h"
@@ -24,10 +29,11 @@
 // ---- Fq: one lane per element ----------------------------------------------------------------------------------------------------------
 struct ZkF1 {
   typedef Fq29 E;
-  template <int VB> static ZK_HD E mul(const E& a, const E& b) { return fq29_mul(a, b); }
-  template <int VA> static ZK_HD E sqr(const E& a) { return fq29_sqr(a); }
+  static constexpr int VY = 2;          // the value bound of a stored Y (Xyzz29)
+  template <int VB> static ZK_HD E mul(const E& a, const E& b) { ZKQ29_NEED_V(b, VB); return fq29_mul(a, b); }
+  template <int VA> static ZK_HD E sqr(const E& a) { ZKQ29_NEED_V(a, VA); return fq29_sqr(a); }
   // a b - c d with ONE reduction: d = [1, <= VD], Ua Ub + 2 Uc <= 6; the result is normalised
-  template <int VB, int VD> static ZK_HD E msub(const E& a, const E& b, const E& c, const E& d) { return fq29_dot2(a, b, c, fq29_neg<VD + 1, 1>(d)); }
+  template <int VB, int VD> static ZK_HD E msub(const E& a, const E& b, const E& c, const E& d) { ZKQ29_NEED_V(b, VB); ZKQ29_NEED_V(d, VD); return fq29_dot2(a, b, c, fq29_neg<VD + 1, 1>(d)); }
   static ZK_HD E scale(const E& a, const Fq29& k) { return fq29_mul(a, k); }
   static ZK_HD E add(const E& a, const E& b) { return fq29_add(a, b); }
   static ZK_HD E dbl(const E& a) { return fq29_dbl(a); }
@@ -51,6 +57,7 @@ __device__ __forceinline__ Fq29 zk_pair_xchg(const Fq29& a) {
 }
 struct ZkF2 {
   typedef Fq29 E;                       // this lane's half: c0 on even lanes, c1 on odd lanes
+  static constexpr int VY = 7;
   static __device__ __forceinline__ bool odd() { return (threadIdx.x & 1u) != 0; }
   template <int VB> static __device__ __forceinline__ E mul(const E& a, const E& b) {
     const Fq29 oa = zk_pair_xchg(a), ob = zk_pair_xchg(b);
@@ -79,9 +86,19 @@ struct ZkF2 {
 };
 #else
 struct Fq29x2 { Fq29 c[2]; };
+#if defined(ZKQ29_SHADOW)
+static inline void zk_q29_claim(const Fq29x2& x, unsigned long long U, double V, bool check) { zk_q29_claim(x.c[0], U, V, check); zk_q29_claim(x.c[1], U, V, check); }
+template <> struct ZkQ29In<Fq29x2> {
+  ZkQ29In<Fq29> a, b;
+  ZkQ29In(const Fq29x2& x, unsigned long long U, double V) : a(x.c[0], U, V), b(x.c[1], U, V) {}
+};
+static inline void zk_q29_need_v(const Fq29x2& a, unsigned long long V) { zk_q29_need_v(a.c[0], V); zk_q29_need_v(a.c[1], V); }
+#endif
 struct ZkF2 {
   typedef Fq29x2 E;
+  static constexpr int VY = 7;
   template <int VB> static inline E mul(const E& a, const E& b) {
+    ZKQ29_NEED_V(b, VB);
     return E{{fq29_dot2(a.c[0], b.c[0], a.c[1], fq29_neg<VB + 1, 1>(b.c[1])), fq29_dot2(a.c[1], b.c[0], a.c[0], b.c[1])}};
   }
   template <int VA> static inline E sqr(const E& a) { return mul<VA>(a, a); }
@@ -103,14 +120,27 @@ struct ZkF2 {
 template <class F> struct Aff29 { typename F::E x, y; bool inf; };          // x [1, 1], y [2, 2] (the negated y of a negative digit is 2 q - y, unnormalised)
 template <class F> struct alignas(16) Xyzz29 { typename F::E x, y, zz, zzz; };          // X [1, 11], Y [1, 7], ZZ, ZZZ [1, 2]; ZZ all zero = infinity
 
+// the two contracts as claims of the host check build (zkwg_fq29.h ZKQ29_CLAIM; nothing anywhere else): checked, then widened to exactly
+// these bounds, so every formula below is proved from the top of its contract whatever its caller passed, and checked to stay inside it
+// (the _IN forms, for the operands: declarations that give the caller's bounds back at the end of the formula)
+#define ZKEC29_CLAIM_AFF_IN(p) ZKQ29_CLAIM_IN((p).x, 1, 1); ZKQ29_CLAIM_IN((p).y, 2, 2)
+#define ZKEC29_CLAIM_XYZZ_IN(F, p) ZKQ29_CLAIM_IN((p).x, 1, 11); ZKQ29_CLAIM_IN((p).y, 1, F::VY); ZKQ29_CLAIM_IN((p).zz, 1, 2); ZKQ29_CLAIM_IN((p).zzz, 1, 2)
+#define ZKEC29_CLAIM_XYZZ(F, p) do { ZKQ29_CLAIM((p).x, 1, 11); ZKQ29_CLAIM((p).y, 1, F::VY); ZKQ29_CLAIM((p).zz, 1, 2); ZKQ29_CLAIM((p).zzz, 1, 2); } while (0)
+
 template <class F> ZK_HD Xyzz29<F> ec29_inf() { return Xyzz29<F>{F::zero(), F::zero(), F::zero(), F::zero()}; }
 template <class F> ZK_HD bool ec29_is_inf(const Xyzz29<F>& p) { return F::all_zero(p.zz); }
-template <class F> ZK_HD Xyzz29<F> ec29_from_affine(const Aff29<F>& p) { return p.inf ? ec29_inf<F>() : Xyzz29<F>{p.x, F::norm(p.y), F::one(), F::one()}; }
+template <class F> ZK_HD Xyzz29<F> ec29_from_affine(const Aff29<F>& p) {
+  ZKEC29_CLAIM_AFF_IN(p);
+  const Xyzz29<F> r = p.inf ? ec29_inf<F>() : Xyzz29<F>{p.x, F::norm(p.y), F::one(), F::one()};
+  ZKEC29_CLAIM_XYZZ(F, r);
+  return r;
+}
 
 // 2 P for an affine P (the equal-points case of a mixed addition: rare, not tuned)
 template <class F>
 ZK_HD Xyzz29<F> ec29_dbl_affine(const Aff29<F>& p) {
   typedef typename F::E E;
+  ZKEC29_CLAIM_AFF_IN(p);
   if (p.inf) return ec29_inf<F>();
   const E py = F::norm(p.y);                                      // [1, 2]
   if (F::template is_zero_mod<2>(py)) return ec29_inf<F>();       // (no point of order 2 on these curves; kept for completeness)
@@ -126,12 +156,14 @@ ZK_HD Xyzz29<F> ec29_dbl_affine(const Aff29<F>& p) {
   const E T = F::template sub<12, 1>(S, r.x);                     // [3, 14]
   r.y = F::template msub<14, 2>(M, T, W, py);                     // [1, 7]
   r.zz = V; r.zzz = W;
+  ZKEC29_CLAIM_XYZZ(F, r);
   return r;
 }
 // 2 P
 template <class F>
 ZK_HD Xyzz29<F> ec29_dbl(const Xyzz29<F>& p) {
   typedef typename F::E E;
+  ZKEC29_CLAIM_XYZZ_IN(F, p);
   if (ec29_is_inf(p)) return p;
   const E U = F::norm(F::dbl(p.y));                               // [1, 14]
   const E V = F::template sqr<14>(U);                             // [1, 4]
@@ -146,12 +178,15 @@ ZK_HD Xyzz29<F> ec29_dbl(const Xyzz29<F>& p) {
   r.y = F::template msub<14, 7>(M, T, W, p.y);                    // [1, 7]
   r.zz = F::template mul<2>(V, p.zz);
   r.zzz = F::template mul<2>(W, p.zzz);
+  ZKEC29_CLAIM_XYZZ(F, r);
   return r;
 }
 // acc + P for an affine P: 7 M + 2 S + one two-product dot product, three carry normalisations
 template <class F>
 ZK_HD Xyzz29<F> ec29_add_mixed(const Xyzz29<F>& a, const Aff29<F>& p) {
   typedef typename F::E E;
+  ZKEC29_CLAIM_XYZZ_IN(F, a);
+  ZKEC29_CLAIM_AFF_IN(p);
   if (p.inf) return a;
   if (ec29_is_inf(a)) return Xyzz29<F>{p.x, F::norm(p.y), F::one(), F::one()};
   // (ordered so that an input dies as early as possible: x2, y2, then ZZ1, X1, ZZZ1, Y1 -- the kernels' register budget)
@@ -170,12 +205,15 @@ ZK_HD Xyzz29<F> ec29_add_mixed(const Xyzz29<F>& a, const Aff29<F>& p) {
   r.x = F::norm(F::template sub<5, 2>(F::template sub<3, 1>(RR, PPP), F::dbl(Q)));     // [6, 11] -> [1, 11]
   const E T = F::template sub<12, 1>(Q, r.x);                     // [3, 14]
   r.y = F::template msub<14, 2>(Rr, T, a.y, PPP);                 // R (Q - X3) - Y1 PPP: [1, 7] (G1: [1, 2])
+  ZKEC29_CLAIM_XYZZ(F, r);
   return r;
 }
 // a + b: 11 M + 2 S + one two-product dot product
 template <class F>
 ZK_HD Xyzz29<F> ec29_add(const Xyzz29<F>& a, const Xyzz29<F>& b) {
   typedef typename F::E E;
+  ZKEC29_CLAIM_XYZZ_IN(F, a);
+  ZKEC29_CLAIM_XYZZ_IN(F, b);
   if (ec29_is_inf(a)) return b;
   if (ec29_is_inf(b)) return a;
   const E U1 = F::template mul<2>(a.x, b.zz);                                              // [1, 2]
@@ -195,6 +233,7 @@ ZK_HD Xyzz29<F> ec29_add(const Xyzz29<F>& a, const Xyzz29<F>& b) {
   r.x = F::norm(F::template sub<5, 2>(F::template sub<3, 1>(RR, PPP), F::dbl(Q)));     // [1, 10]
   const E T = F::template sub<12, 1>(Q, r.x);                     // [3, 14]
   r.y = F::template msub<14, 2>(Rr, T, S1, PPP);                  // [1, 7]
+  ZKEC29_CLAIM_XYZZ(F, r);
   return r;
 }
 
@@ -208,6 +247,13 @@ ZK_HD Fq29 zk_q29_neg_if(const Fq29& y, bool neg) {
   Fq29 r;
 #pragma unroll
   for (int i = 0; i < 9; ++i) r.l[i] = neg ? n.l[i] : y.l[i];
+  ZKQ29_SELECT(r, neg ? n : y, y);          // a negated y is [2, 2] (the larger of both bounds); with neg = false the result IS y, [1, 1] as loaded
+  return r;
+}
+// a coordinate of a table-form base in limb form: [1, 1]
+ZK_HD Fq29 zk_q29_base(const Fq& a) {
+  const Fq29 r = fq29_from_fq(a);
+  ZKQ29_ASSUME(r, 1, 1);          // relies on: tables hold canonical words -- zk_fq_r256_to_r261 / fq29_to_fq reduce below q, and a point read from a file passed zk_setup_prepare_point's coordinate < q check
   return r;
 }
 // one coordinate (32 bytes, 16-byte aligned: tables come from hipMalloc) as two 16-byte loads
@@ -227,7 +273,7 @@ struct ZkEcG1 {
   static constexpr int DEV_LANES = 1;      // lanes per point in the kernels (what the host sizes its launches with)
   static ZK_HD Aff29<F> load(const Affine* p, u32 h, bool neg) {
     const Fq x = zk_ld_fq(&p->x), y = zk_ld_fq(&p->y);
-    return Aff29<F>{fq29_from_fq(x), zk_q29_neg_if(fq29_from_fq(y), neg), fq_is_zero(x) && fq_is_zero(y)};
+    return Aff29<F>{zk_q29_base(x), zk_q29_neg_if(zk_q29_base(y), neg), fq_is_zero(x) && fq_is_zero(y)};
   }
   static ZK_HD void store_out(Out* o, const Xyzz29<F>& p, u32 h) {
     const Fq29 k = fq29_r256();
@@ -246,7 +292,7 @@ struct ZkEcG2 {
     const Fq* w = (const Fq*)p;                      // x.c0 | x.c1 | y.c0 | y.c1
     const Fq x = zk_ld_fq(w + h), y = zk_ld_fq(w + 2 + h);
     const bool z = F::both(fq_is_zero(x) && fq_is_zero(y));
-    return Aff29<F>{fq29_from_fq(x), zk_q29_neg_if(fq29_from_fq(y), neg), z};
+    return Aff29<F>{zk_q29_base(x), zk_q29_neg_if(zk_q29_base(y), neg), z};
   }
   static __device__ __forceinline__ void store_out(Out* o, const Xyzz29<F>& p, u32 h) {
     const Fq29 k = fq29_r256();
@@ -258,7 +304,7 @@ struct ZkEcG2 {
   static constexpr int LANES = 1;
   static inline Aff29<F> load(const Affine* p, u32 h, bool neg) {
     const Affine a = *p;
-    return Aff29<F>{Fq29x2{{fq29_from_fq(a.x.c0), fq29_from_fq(a.x.c1)}}, Fq29x2{{zk_q29_neg_if(fq29_from_fq(a.y.c0), neg), zk_q29_neg_if(fq29_from_fq(a.y.c1), neg)}}, g2_is_inf(a)};
+    return Aff29<F>{Fq29x2{{zk_q29_base(a.x.c0), zk_q29_base(a.x.c1)}}, Fq29x2{{zk_q29_neg_if(zk_q29_base(a.y.c0), neg), zk_q29_neg_if(zk_q29_base(a.y.c1), neg)}}, g2_is_inf(a)};
   }
   static inline void store_out(Out* o, const Xyzz29<F>& p, u32 h) {
     const Fq29 k = fq29_r256();

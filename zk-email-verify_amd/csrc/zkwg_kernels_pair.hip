@@ -29,6 +29,7 @@ __global__ __launch_bounds__(64) void zk_pair_product(const Fq* f, const u8* use
     const bool on = i < n && (!use || use[i] != 0);             // (the same for both lanes of the pair)
     const ZkF12 x = zk_f12_load(f + 12ull * (on ? i : 0u), h);  // (index 0 exists: n >= 1 here)
     acc = zk_f12_mul(acc, zk_f12_select(on, x, zk_f12_one()));
+    ZKF12_CLAIM(acc, 5, 2, ZK_F12_MUL_V5);                        // (the host build of this loop checks it: tests/native/pairtest.cpp pt_pair_product)
   }
   zk_f12_store(out + 12ull * j, acc, h);
 }

@@ -17,15 +17,26 @@
 //             instructions on meaningless values: nothing is indexed or looped on data, so such a pair cannot fault or hang; its value is
 //             ignored by the caller (the `inside` flag) or replaced by 1 (infinity on either side: f = 1 exactly).
 //
-// BOUNDS ([U, V] of zkwg_fq29.h).  Every Fq2 product is a reduced dot product: [1, 2] for Va Vb <= 169.  A coefficient of an Fq12 is
-// [1, 12] AT MOST, which is what every product below assumes of its operands (12 x 12 = 144 <= 169):
-//     c_k = lo_k + xi hi_k,  lo_k = sum of the products a_i b_j with i + j = k (at most 6: [6, 12]),  hi_k those with i + j = k + 6 (at
-//     most 5: [5, 10], normalised [1, 10]).  xi a = 9 a + i a for a = [1, V]: 4 a normalised [1, 4 V], 8 a + a [3, 9 V], plus the
-//     partner's half or its negation [2, V + 1]: [5, 10 V + 1], normalised.  So lo_k + xi hi_k = [7, 113], normalised, and ONE product with
-//     the constant 1 (an Fq product per lane: half an Fq2 product) brings it back to [1, 2].  c_5 has no hi part: [1, 12] normalised, no product.
-// The sparse product has hi parts only for k < 3 (at most 2 terms: [1, 4] -> xi [1, 41]; lo + xi hi = [3, 45]); k >= 3 are sums of 3: [1, 6].
-// T keeps the bounds of Xyzz29 (X [1, 11], Y [1, 7], ZZ, ZZZ [1, 2]) as an invariant of both steps; line coefficients are right operands:
-// l0, l1 [1, 2], l3 [1, 9] (tangent) / [1, 5] (chord), 12 x 9 = 108 <= 169.  The bound of every intermediate is written beside it.
+// BOUNDS ([U, V] of zkwg_fq29.h), as the host check build PROVES them: every function below claims its operands' and its results' bounds
+// (ZKQ29_CLAIM / ZKQ29_CLAIM_IN: checked, then widened to exactly the claim), so one call is the function at the top of its contract, and
+// tests/test_fq29_bounds_cpu.py makes that call for each of them.  An Fq2 product F::mul<VB>(a, b) is one reduced two-product dot product
+// per half, and the even half negates the partner's half with (VB + 1) q WHATEVER b's own bound is: its value is below
+// (Va Vb + Va (VB + 1)) / 169.28 + 1 q (169.28 = 2^261 / q) -- 1.18 q for [1, 2] x [1, 2] under mul<12>, 2.77 q for [1, 12] x [1, 12], not
+// "[1, 2] whenever Va Vb <= 169".  Per function:
+//     zk_f12_sqr       operand c0 .. c2 [1, 2], c3 .. c5 [1, 6] (what zk_f12_mul_line returns); result c0 .. c4 [1, 2], c5 [1, 12]
+//     zk_f12_mul_line  operand c0 .. c4 [1, 6], c5 [1, 12] (f^2, or an earlier f l); l0, l1 [1, 2], l3 [1, 9]; result c0 .. c2 [1, 2], c3 .. c5 [1, 6]
+//     zk_f12_mul       operands AND result c0 .. c4 [1, 2], c5 [1, 8] (ZK_F12_MUL_V5): closed under itself, which the loop of zk_pair_product
+//                      needs (zk_f12_load gives [1, 2]; the accumulator is claimed after every product).  NOT [1, 12]: six such terms reach
+//                      16.7 q in lo, and c5 = norm(lo) with them.
+//     c_k = lo_k + xi hi_k,  lo_k = sum of the products a_i b_j with i + j = k (at most 6),  hi_k those with i + j = k + 6 (at most 5, below
+//     10 q, normalised).  xi a = 9 a + i a for a = [1, V]: 4 a normalised [1, 4 V], 8 a + a [3, 9 V], plus the partner's half or its
+//     negation [2, V + 1]: [5, 10 V + 1], normalised.  So lo_k + xi hi_k stays below 169 q, normalised, and ONE product with the constant 1
+//     (an Fq product per lane: half an Fq2 product) brings it back to [1, 2].  c_5 has no hi part: lo normalised, no product.
+// The sparse product has hi parts only for k < 3 (at most 2 terms -> xi<4>); k >= 3 are sums of 3: [1, 6].
+// T: X [1, 10.25], Y [1, 7], ZZ, ZZZ [1, 2], an invariant of both steps (a doubling leaves X below 6.8 q, an addition below 10.1 q).  With
+// Xyzz29's X [1, 11] the tangent's l3 = 2 M X - U^2 + 5 q could reach 9.006 q, above the 9 q that mul<9> (its negation constant 10 q) allows: the claim
+// on T.X is what makes l3 [1, 9] true.  Line coefficients are right operands: l0, l1 [1, 2], l3 [1, 9] (tangent) / [1, 5] (chord).  The
+// bound of every intermediate is written beside it.
 //
 // COST PER PAIR in Fq2 products (counted as zkwg_verify_core.h counts: a square = a product, the two-product dot product = 2, a product
 // with an Fq value = 1/2):
@@ -41,6 +52,7 @@
 #include "zkwg_verify_core.h"
 
 #define ZK_PAIR_MAX (1u << 20)        // pairs per launch
+#define ZK_F12_MUL_V5 8               // the value bound of coefficient 5 of zk_f12_mul's operands and result (BOUNDS below)
 #define ZK_PAIR_FOLD 4u               // values one lane pair of zk_pair_product multiplies
 #define ZK_PAIR_LOOP_LOW (6ull * ZK_VERIFY_U + 2ull)      // bits 0 .. 63 of 6 u + 2 (the product wraps: bit 64, the top one, is implied)
 
@@ -74,6 +86,13 @@ template <int VH> ZK_HD ZkF2::E zk_pair_fold(const ZkF2::E& lo, const ZkF2::E& h
   return zk_pair_red(F::norm(F::add(lo, zk_pair_xi<VH>(F::norm(hi)))));
 }
 
+// the stated bounds of an Fq12's coefficients as claims (host check build; nothing elsewhere): coefficients 0 .. N - 1 [1, VLO], the others [1, VHI]
+#define ZKF12_CLAIM(f, N, VLO, VHI) do { ZKQ29_CLAIM((f).c[0], 1, 0 < (N) ? (VLO) : (VHI)); ZKQ29_CLAIM((f).c[1], 1, 1 < (N) ? (VLO) : (VHI)); ZKQ29_CLAIM((f).c[2], 1, 2 < (N) ? (VLO) : (VHI)); \
+    ZKQ29_CLAIM((f).c[3], 1, 3 < (N) ? (VLO) : (VHI)); ZKQ29_CLAIM((f).c[4], 1, 4 < (N) ? (VLO) : (VHI)); ZKQ29_CLAIM((f).c[5], 1, 5 < (N) ? (VLO) : (VHI)); } while (0)
+#define ZKF12_CLAIM_IN(f, N, VLO, VHI) ZKQ29_CLAIM_IN((f).c[0], 1, 0 < (N) ? (VLO) : (VHI)); ZKQ29_CLAIM_IN((f).c[1], 1, 1 < (N) ? (VLO) : (VHI)); ZKQ29_CLAIM_IN((f).c[2], 1, 2 < (N) ? (VLO) : (VHI)); \
+    ZKQ29_CLAIM_IN((f).c[3], 1, 3 < (N) ? (VLO) : (VHI)); ZKQ29_CLAIM_IN((f).c[4], 1, 4 < (N) ? (VLO) : (VHI)); ZKQ29_CLAIM_IN((f).c[5], 1, 5 < (N) ? (VLO) : (VHI))
+#define ZKPAIR_CLAIM_T(t) do { ZKQ29_CLAIM((t).x, 1, 10.25); ZKQ29_CLAIM((t).y, 1, 7); ZKQ29_CLAIM((t).zz, 1, 2); ZKQ29_CLAIM((t).zzz, 1, 2); } while (0)
+
 static ZK_HD ZkF12 zk_f12_one() {
   ZkF12 r;
 #pragma unroll
@@ -85,10 +104,10 @@ static ZK_HD ZkF12 zk_f12_one() {
 // term a_I b_(K - I) of coefficient K of a b, to lo, or a_I b_(K + 6 - I), to hi
 template <int K, int I> ZK_HD void zk_f12_mul_term(const ZkF12& a, const ZkF12& b, ZkF2::E& lo, ZkF2::E& hi) {
   typedef ZkF2 F;
-  if constexpr (I <= K) lo = F::add(lo, F::mul<12>(a.c[I], b.c[K - I]));          // <= [6, 12]
-  else hi = F::add(hi, F::mul<12>(a.c[I], b.c[K + 6 - I]));                       // <= [5, 10]
+  if constexpr (I <= K) lo = F::add(lo, F::mul<12>(a.c[I], b.c[K - I]));          // <= [6, 8] (operands as zk_f12_mul states them)
+  else hi = F::add(hi, F::mul<12>(a.c[I], b.c[K + 6 - I]));                       // <= [5, 7]
 }
-// coefficient K of a b, both [1, 12]: K < 5 [1, 2], K = 5 [1, 12]
+// coefficient K of a b, both c0 .. c4 [1, 2], c5 [1, 8]: K < 5 [1, 2], K = 5 [1, 8]
 template <int K> ZK_HD ZkF2::E zk_f12_mul_coeff(const ZkF12& a, const ZkF12& b) {
   typedef ZkF2 F;
   F::E lo = F::zero(), hi = F::zero();
@@ -99,8 +118,11 @@ template <int K> ZK_HD ZkF2::E zk_f12_mul_coeff(const ZkF12& a, const ZkF12& b) 
 }
 static ZK_HD ZkF12 zk_f12_mul(const ZkF12& a, const ZkF12& b) {
   ZkF12 r;
+  ZKF12_CLAIM_IN(a, 5, 2, ZK_F12_MUL_V5);
+  ZKF12_CLAIM_IN(b, 5, 2, ZK_F12_MUL_V5);
   r.c[0] = zk_f12_mul_coeff<0>(a, b); r.c[1] = zk_f12_mul_coeff<1>(a, b); r.c[2] = zk_f12_mul_coeff<2>(a, b);
   r.c[3] = zk_f12_mul_coeff<3>(a, b); r.c[4] = zk_f12_mul_coeff<4>(a, b); r.c[5] = zk_f12_mul_coeff<5>(a, b);
+  ZKF12_CLAIM(r, 5, 2, ZK_F12_MUL_V5);
   return r;
 }
 // the cross products a_I a_J, I < J, of coefficient K of a a: J = K - I to lo, J = K + 6 - I to hi
@@ -124,11 +146,13 @@ template <int K> ZK_HD ZkF2::E zk_f12_sqr_coeff(const ZkF12& a) {
 }
 static ZK_HD ZkF12 zk_f12_sqr(const ZkF12& a) {
   ZkF12 r;
+  ZKF12_CLAIM_IN(a, 3, 2, 6);
   r.c[0] = zk_f12_sqr_coeff<0>(a); r.c[1] = zk_f12_sqr_coeff<1>(a); r.c[2] = zk_f12_sqr_coeff<2>(a);
   r.c[3] = zk_f12_sqr_coeff<3>(a); r.c[4] = zk_f12_sqr_coeff<4>(a); r.c[5] = zk_f12_sqr_coeff<5>(a);
+  ZKF12_CLAIM(r, 5, 2, 12);
   return r;
 }
-// coefficient K of f (l0 + l1 w + l3 w^3) for f = [1, 12], l = [1, <= 9]: K < 3 [1, 2], K >= 3 [1, 6]
+// coefficient K of f (l0 + l1 w + l3 w^3) for f = c0 .. c4 [1, 6], c5 [1, 12], l = [1, <= 9]: K < 3 [1, 2], K >= 3 [1, 6]
 template <int K> ZK_HD ZkF2::E zk_f12_line_coeff(const ZkF12& f, const ZkPairLine& l) {
   typedef ZkF2 F;
   F::E lo = F::mul<9>(f.c[K], l.l0), hi = F::zero();
@@ -139,8 +163,11 @@ template <int K> ZK_HD ZkF2::E zk_f12_line_coeff(const ZkF12& f, const ZkPairLin
 }
 static ZK_HD ZkF12 zk_f12_mul_line(const ZkF12& f, const ZkPairLine& l) {
   ZkF12 r;
+  ZKF12_CLAIM_IN(f, 5, 6, 12);
+  ZKQ29_CLAIM_IN(l.l0, 1, 2); ZKQ29_CLAIM_IN(l.l1, 1, 2); ZKQ29_CLAIM_IN(l.l3, 1, 9);
   r.c[0] = zk_f12_line_coeff<0>(f, l); r.c[1] = zk_f12_line_coeff<1>(f, l); r.c[2] = zk_f12_line_coeff<2>(f, l);
   r.c[3] = zk_f12_line_coeff<3>(f, l); r.c[4] = zk_f12_line_coeff<4>(f, l); r.c[5] = zk_f12_line_coeff<5>(f, l);
+  ZKF12_CLAIM(r, 3, 2, 6);
   return r;
 }
 
@@ -148,6 +175,8 @@ static ZK_HD ZkF12 zk_f12_mul_line(const ZkF12& f, const ZkPairLine& l) {
 static ZK_HD ZkPairLine zk_pair_dbl_step(Xyzz29<ZkF2>& t, const Fq29& yP, const Fq29& nxP) {
   typedef ZkF2 F;
   typedef F::E E;
+  ZKPAIR_CLAIM_T(t);
+  ZKQ29_CLAIM_IN(yP, 1, 1); ZKQ29_CLAIM_IN(nxP, 1, 2);
   const E U = F::norm(F::dbl(t.y));                               // [1, 14]
   const E V = F::sqr<14>(U);                                      // [1, 4]
   const E W = F::mul<4>(U, V);                                    // [1, 2]
@@ -166,12 +195,16 @@ static ZK_HD ZkPairLine zk_pair_dbl_step(Xyzz29<ZkF2>& t, const Fq29& yP, const 
   r.zz = F::mul<2>(V, t.zz);
   r.zzz = F::mul<2>(W, t.zzz);
   t = r;
+  ZKPAIR_CLAIM_T(t);
+  ZKQ29_CLAIM(l.l0, 1, 2); ZKQ29_CLAIM(l.l1, 1, 2); ZKQ29_CLAIM(l.l3, 1, 9);
   return l;
 }
 // T <- T + Q and the chord through them at P, Q = (x2, y2) affine, both [1, <= 2]
 static ZK_HD ZkPairLine zk_pair_add_step(Xyzz29<ZkF2>& t, const ZkF2::E& x2, const ZkF2::E& y2, const Fq29& yP, const Fq29& nxP) {
   typedef ZkF2 F;
   typedef F::E E;
+  ZKPAIR_CLAIM_T(t);
+  ZKQ29_CLAIM_IN(x2, 1, 2); ZKQ29_CLAIM_IN(y2, 1, 2); ZKQ29_CLAIM_IN(yP, 1, 1); ZKQ29_CLAIM_IN(nxP, 1, 2);
   const E P = F::norm(F::sub<12, 1>(F::mul<2>(x2, t.zz), t.x));   // [1, 14]
   const E Rr = F::norm(F::sub<8, 1>(F::mul<2>(y2, t.zzz), t.y));  // [1, 10]
   const E D = F::mul<2>(P, t.zzz), Ee = F::mul<2>(Rr, t.zz);      // [1, 2]
@@ -190,6 +223,8 @@ static ZK_HD ZkPairLine zk_pair_add_step(Xyzz29<ZkF2>& t, const ZkF2::E& x2, con
   const E T = F::sub<12, 1>(Q, r.x);                              // [3, 14]
   r.y = F::msub<14, 2>(Rr, T, t.y, PPP);                          // [1, 7]
   t = r;
+  ZKPAIR_CLAIM_T(t);
+  ZKQ29_CLAIM(l.l0, 1, 2); ZKQ29_CLAIM(l.l1, 1, 2); ZKQ29_CLAIM(l.l3, 1, 5);
   return l;
 }
 
@@ -246,7 +281,11 @@ static ZK_HD ZkF12 zk_f12_load(const Fq* w, u32 h) {
 static ZK_HD void zk_f12_store(Fq* w, const ZkF12& f, u32 h) {
   for (int k = 0; k < 6; ++k) for (int j = 0; j < 2; ++j) w[2 * k + j] = fq29_to_fq<2>(fq29_mul(f.c[k].c[j], fq29_r256()));
 }
-static ZK_HD ZkF12 zk_f12_select(bool first, const ZkF12& a, const ZkF12& b) { return first ? a : b; }
+static ZK_HD ZkF12 zk_f12_select(bool first, const ZkF12& a, const ZkF12& b) {
+  ZkF12 r = first ? a : b;
+  for (int k = 0; k < 6; ++k) for (int j = 0; j < 2; ++j) ZKQ29_SELECT(r.c[k].c[j], a.c[k].c[j], b.c[k].c[j]);
+  return r;
+}
 #endif
 
 // the pair (p, q) of table-form points, half h of a lane pair: out = the Miller value (1 when either is infinity); returns whether q is
@@ -256,7 +295,7 @@ static ZK_HD bool zk_pair_miller_point(const G1Affine* p, const G2Affine* q, u32
   const Fq px = zk_ld_fq(&p->x), py = zk_ld_fq(&p->y);
   const Aff29<F> Q = ZkEcG2::load(q, h, false);                   // x [1, 1], y [1, 1]
   const bool inf = Q.inf || (fq_is_zero(px) && fq_is_zero(py));
-  const ZkF12 f = zk_pair_miller_loop(Q.x, Q.y, fq29_from_fq(px), fq29_from_fq(py));
+  const ZkF12 f = zk_pair_miller_loop(Q.x, Q.y, zk_q29_base(px), zk_q29_base(py));
   zk_f12_store(out, zk_f12_select(inf, zk_f12_one(), f), h);
   return zk_verify_g2_in_subgroup(q, h, Du);
 }

@@ -369,6 +369,7 @@ ZK_HD Fq29 zk_setup_curve_b(ZkEcG1) { return zk_setup_b_g1(); }
 template <class C>
 ZK_HD bool zk_setup_on_curve(const typename C::F::E& x, const typename C::F::E& y) {
   typedef typename C::F F;
+  ZKQ29_ASSUME(x, 1, 1); ZKQ29_ASSUME(y, 1, 1);          // relies on: every caller passes words out of zk_fq_r256_to_r261, whose fq29_to_fq<2> reduces below q
   const typename F::E y2 = F::template sqr<1>(y);                                       // [1, 2]
   const typename F::E x3 = F::template mul<1>(F::template sqr<1>(x), x);                // [1, 2]
   const typename F::E rhs = F::add(x3, zk_setup_curve_b(C()));                          // [2, 3]

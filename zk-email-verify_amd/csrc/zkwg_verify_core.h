@@ -81,6 +81,7 @@ template <int V> static inline Fq29x2 zk_verify_conj(const Fq29x2& a) { return F
 template <int K>
 ZK_HD Xyzz29<ZkF2> zk_verify_psi(const Xyzz29<ZkF2>& a) {
   typedef ZkF2 F;
+  ZKEC29_CLAIM_XYZZ_IN(F, a);
   if (ec29_is_inf<F>(a)) return a;
   const F::E cx = K == 1 ? zk_verify_const(zk_verify_cx1_c0(), zk_verify_cx1_c1()) : zk_verify_const(zk_verify_cx3_c0(), zk_verify_cx3_c1());
   const F::E cy = K == 1 ? zk_verify_const(zk_verify_cy1_c0(), zk_verify_cy1_c1()) : zk_verify_const(zk_verify_cy3_c0(), zk_verify_cy3_c1());
@@ -94,6 +95,7 @@ ZK_HD Xyzz29<ZkF2> zk_verify_psi(const Xyzz29<ZkF2>& a) {
 // psi^2: (gamma X, -Y, ZZ, ZZZ)
 static ZK_HD Xyzz29<ZkF2> zk_verify_psi2(const Xyzz29<ZkF2>& a) {
   typedef ZkF2 F;
+  ZKEC29_CLAIM_XYZZ_IN(F, a);
   if (ec29_is_inf<F>(a)) return a;
   return Xyzz29<F>{F::scale(a.x, zk_verify_gamma()), F::scale(a.y, zk_verify_minus_one()), a.zz, a.zzz};      // [1, 11] x [1, 1], [1, 7] x [1, 1] -> [1, 2]
 }
@@ -101,6 +103,8 @@ static ZK_HD Xyzz29<ZkF2> zk_verify_psi2(const Xyzz29<ZkF2>& a) {
 static ZK_HD bool zk_verify_same_point(const Xyzz29<ZkF2>& a, const Xyzz29<ZkF2>& b) {
   typedef ZkF2 F;
   const bool ia = ec29_is_inf<F>(a), ib = ec29_is_inf<F>(b);
+  ZKEC29_CLAIM_XYZZ_IN(F, a);
+  ZKEC29_CLAIM_XYZZ_IN(F, b);
   if (ia || ib) return ia && ib;
   const F::E ex = F::sub<3, 1>(F::mul<2>(a.x, b.zz), F::mul<2>(b.x, a.zz));            // [1, 2] - [1, 2] -> [3, 5]
   const F::E ey = F::sub<3, 1>(F::mul<2>(a.y, b.zzz), F::mul<2>(b.y, a.zzz));
@@ -113,10 +117,13 @@ static ZK_HD bool zk_verify_g2_in_subgroup(const G2Affine* p, u32 h, const ZkPha
   const Aff29<F> Q = ZkEcG2::load(p, h, false);                   // x [1, 1], y [1, 1]
   if (Q.inf) return true;
   const Xyzz29<F> A = zk_phase2_scale_point<ZkEcG2>(p, h, Du);    // [u] Q: X [1, 11], Y [1, 7]
+  ZKEC29_CLAIM_XYZZ(F, A);
   Xyzz29<F> L = ec29_add_mixed<F>(A, Q);                          // X [1, 11], Y [1, 7]
   L = ec29_add<F>(L, zk_verify_psi<1>(A));                        // X [1, 10], Y [1, 7]
   L = ec29_add<F>(L, zk_verify_psi2(A));
+  ZKEC29_CLAIM_XYZZ(F, L);
   const Xyzz29<F> Rr = zk_verify_psi<3>(ec29_dbl<F>(A));
+  ZKEC29_CLAIM_XYZZ(F, Rr);
   return zk_verify_same_point(L, Rr);
 }
 
