@@ -774,7 +774,8 @@ int zkwg_point_rlc32_device(int device, int group, const void* d_a, const void* 
  * The device runs what grows with the batch -- one Miller loop per proof on a lane pair, the subgroup test of its B_i, the scalings
  * r_i A_i and r_i C_i, the product tree; the host adds three Miller loops and ONE final exponentiation per check.  When the batch
  * check fails the host bisects over the per-proof values (downloaded once, the same r_i): with k bad proofs among n at most
- * min(2 n - 1, 1 + 2 k ceil(log2 n)) checks.  A batch of mostly bad proofs is slow by design.
+ * min(2 n - 1, 1 + 2 k ceil(log2 n)) checks.  A batch of mostly bad proofs is slow by design: zkwg_groth16_verify_each (below) is the call
+ * for proofs that may be bad.
  *
  * zkwg_miller_device: f[i] = Miller value of (g1[i], g2[i]) up to a factor in Fq2 (the final exponentiation removes it: FE(f[i]) is the
  * reduced pairing); inside[i] = g2[i] in the subgroup of order r (f[i] means nothing when it is not).  Device pointers, the zkey's point form
@@ -806,6 +807,32 @@ typedef struct zkwg_verification_key {
 int zkwg_groth16_verify_batch(int device, const zkwg_verification_key* vk, uint64_t n, const uint8_t* proofs,
                               const uint8_t* publics, const uint8_t* rand16, uint8_t* ok);
 void zkwg_groth16_verify_stats(double seconds[6], uint64_t counts[4]);
+/* Per-proof verdicts (csrc/zkwg_fexp_core.h, csrc/zkwg_fexp_host.h): the final exponentiation on the device, and a verifier whose work
+ * does not depend on how many proofs are bad -- what a service that takes proofs from strangers calls.
+ *
+ * zkwg_final_exp_device: out[i] = FE(f[i]) = f[i]^((q^12 - 1) / r), EXACT (the value of the host's 2,790-bit square-and-multiply, not a
+ * power of it; FE(0) = 0).  n x 384 bytes both ways, the form zkwg_miller_device writes; device pointers, 16-byte aligned; d_out may be
+ * d_f.  n <= 2^20; n = 0 is ZKWG_RC_OK; device < 0: ZKWG_RC_NO_DEVICE.  Easy part with one Fq inversion per value, three powers by u over
+ * its non-adjacent form with Granger-Scott squarings, the hard part by the chain of Devegili, Scott and Dahab: 22 launches with fixed
+ * control flow, the value in device memory between them (2,688 bytes per value, freed before the call returns).
+ *
+ * zkwg_groth16_verify_each: ok[i] = 1 iff proof i verifies, each proof on its own:
+ *     FE( f(A_i, B_i) . f(-vkx_i, gamma) . f(-C_i, delta) ) = e(alpha, beta)  and  B_i in the subgroup of order r,   vkx_i = IC_0 + sum_j x_ij IC_j.
+ * Arguments, per-proof rejections (ok[i] = 0, the call goes on) and refusals of the key as zkwg_groth16_verify_batch, without rand16:
+ * there is no randomness and no bisection.  device >= 0: the scalings x_ij IC_j (zkwg_point_mul_device), their sum made affine by the
+ * complete point formulas (a public input 0, equal and opposite summands; vkx_i at infinity contributes f = 1), three Miller loops per
+ * proof and the final exponentiation of their product on that device; the host makes e(alpha, beta) once per call, by the same final
+ * exponentiation, and compares.  device = -1: the same algorithm on the host alone.  n <= 2^20; the call works in pieces of at most
+ * 349,525 proofs (3 pairs each in one Miller launch; fewer when n_public x proofs would pass 2^20 scaled points).  Device memory per
+ * proof of a piece: 5,187 + 96 n_public bytes beside what zkwg_miller_device (192 per pair) and zkwg_point_mul_device (2,024 per scaled
+ * point) take while they run.
+ * zkwg_groth16_verify_each_stats, of this thread's last call: seconds = {host checks + e(alpha, beta) + upload, vkx, Miller + subgroup,
+ * final exponentiation, download + compare, 0}; counts = {pairs through the Miller loop (3 per proof that passed the host checks),
+ * values exponentiated (those proofs + 1 for e(alpha, beta)), proofs excluded before the device, proofs found bad after that}. */
+int zkwg_final_exp_device(int device, const void* d_f, uint64_t n, void* d_out, void* hip_stream);
+int zkwg_groth16_verify_each(int device, const zkwg_verification_key* vk, uint64_t n, const uint8_t* proofs, const uint8_t* publics,
+                             uint8_t* ok);
+void zkwg_groth16_verify_each_stats(double seconds[6], uint64_t counts[4]);
 
 /* ---- the compact image as a device-side interchange format --------------------------
  * zkwg_prepare_device leaves, per email, a compact IMAGE in the scratch buffer (~0.45 MB instead of the 57 MB

@@ -19,7 +19,8 @@
 // halves: the left half is checked; when it passes, the right half is KNOWN to fail and is not checked, otherwise the left half is known to
 // fail and the right half is checked.  A failing set of one proof is a bad proof.  Every set is checked at most once and a failing set costs at
 // most 2 checks, so with k bad proofs among n the host makes at most  min(2 n - 1, 1 + 2 k ceil(log2 n))  checks, each 3 Miller loops and
-// one final exponentiation.  A batch of mostly bad proofs is slow by design.
+// one final exponentiation.  A batch of mostly bad proofs is slow by design: csrc/zkwg_fexp_host.h (zkwg_groth16_verify_each) is the
+// verifier whose work does not depend on the share of bad proofs.
 #pragma once
 #include <chrono>
 #include <functional>

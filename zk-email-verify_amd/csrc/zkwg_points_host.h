@@ -1,4 +1,4 @@
-// The host scaffold of the key-ceremony device calls: what zkwg_{setup,phase2,ptau,ptau_key,verify,pair}_api.hip (and nothing else) are
+// The host scaffold of the key-ceremony device calls: what zkwg_{setup,phase2,ptau,ptau_key,verify,pair,fexp}_api.hip (and nothing else) are
 // written with.  Every one of those calls is one-shot -- it allocates its device buffers, synchronises and frees everything before it
 // returns -- so they share: the declarations of the launch wrappers, the sizes of a point, the refusal (fail), one owner of device
 // buffers (DevBufs), the read of the fault flags (zk_read_flags), a stage clock, the per-thread statistics (ZkStats) and the check of
@@ -35,6 +35,12 @@ void zk_verify_widen_launch(const void* in, void* out, u64 n, hipStream_t st);
 // zkwg_kernels_pair.hip
 void zk_pair_miller_launch(const void* g1, const void* g2, u32 n, const ZkPhase2Digits& Du, void* f, u8* inside, hipStream_t st);
 void zk_pair_product_launch(const void* f, const u8* use, u32 n, void* out, hipStream_t st);
+// zkwg_kernels_fexp.hip
+void zk_fexp_fold_launch(const void* f, u32 n, u32 k, void* out, hipStream_t st);
+void zk_fexp_ninv_launch(const void* x, const void* y, u32 n, void* out, hipStream_t st);
+void zk_fexp_pow_u_launch(const void* g, u32 n, void* out, hipStream_t st);
+void zk_fexp_step_launch(const void* x, const void* y, u32 n, u32 pre_a, u32 pre_b, u32 post, void* out, hipStream_t st);
+void zk_g16_vkx_launch(const void* ic0, const void* terms, u32 n_terms, u32 n, void* g1, hipStream_t st);
 // zkwg_api.hip
 extern "C" void zk_set_last_error(const char* m);
 

@@ -205,6 +205,9 @@ def load():
         "zkwg_fq12_product_device": (i32, [i32, vp, vp, u64, vp, vp]),
         "zkwg_groth16_verify_batch": (i32, [i32, vp, u64, vp, vp, vp, vp]),
         "zkwg_groth16_verify_stats": (None, [C.POINTER(C.c_double), C.POINTER(u64)]),
+        "zkwg_final_exp_device": (i32, [i32, vp, u64, vp, vp]),
+        "zkwg_groth16_verify_each": (i32, [i32, vp, u64, vp, vp, vp]),
+        "zkwg_groth16_verify_each_stats": (None, [C.POINTER(C.c_double), C.POINTER(u64)]),
         "zkwg_groth16_assemble": (i32, [vp] * 15),
         "zkwg_calculate_batch_resident": (i32, [vp, vp, u64, vp, vp, u64, u64, vp, vp]),
         "zkwg_resident_placement": (i32, [vp, C.POINTER(C.c_float), i32, C.POINTER(C.c_int)]),
@@ -237,4 +240,5 @@ EXPORTS = [
     "zkwg_point_mul_device", "zkwg_point_powers_device", "zkwg_ptau_apply_key_size", "zkwg_ptau_apply_key", "zkwg_ptau_apply_key_stats",
     "zkwg_pairing_check", "zkwg_g2_subgroup_device", "zkwg_point_rlc_device", "zkwg_point_rlc32_device",
     "zkwg_miller_device", "zkwg_fq12_product_device", "zkwg_groth16_verify_batch", "zkwg_groth16_verify_stats",
+    "zkwg_final_exp_device", "zkwg_groth16_verify_each", "zkwg_groth16_verify_each_stats",
 ]

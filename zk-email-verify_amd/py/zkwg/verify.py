@@ -1,4 +1,4 @@
-"""python -m zkwg.verify verification_key.json public.json proof.json [--device D]
+"""python -m zkwg.verify verification_key.json public.json proof.json [--device D] [--each]
 -- `snarkjs groth16 verify` (reference: packages/helpers/src/chunked-zkey.ts:93-101, snarkjs.groth16.verify(vkey, publicSignals, proof)):
 prints OK / INVALID and exits 0 / 1.  public.json and proof.json may also be JSON lists of equal length (a batch): one line per proof,
 exit 1 if any is invalid.
@@ -6,6 +6,10 @@ exit 1 if any is invalid.
 verify_batch checks MANY proofs of one key with one Miller loop per proof on the device and one final exponentiation on the host
 (zkwg_groth16_verify_batch, include/zkwg.h "checking proofs": the batch equation, the per-proof rejections and the bisection that finds
 the bad proofs of a failing batch are stated there and in csrc/zkwg_pair_host.h).  device = -1 runs the same algorithm on the host alone.
+
+verify_each (--each) gives the verdict of every proof on its own: three Miller loops and one final exponentiation per proof, all on the
+device (zkwg_groth16_verify_each), no randomness and no bisection -- its work does not depend on how many proofs are bad, which is what
+a verifier of proofs from strangers needs; verify_batch is the faster call while (nearly) every proof is good.
 
 A malformed argument (wrong lengths, nPublic != len(IC) - 1, a z coordinate that is not 1, not a BN254 groth16 key) raises VerifyError; a
 well-formed but wrong proof gives False.  The key's vk_alphabeta_12 is ignored: e(alpha, beta) is one of the pairs of the product."""
@@ -89,12 +93,8 @@ def proof_bytes(proof):
     return b"".join(v.to_bytes(32, "little") for v in vals)
 
 
-def verify_batch(vkey, publics, proofs, device=0, rand=None):
-    """-> [bool per proof].  vkey: a snarkjs verification_key.json dict; publics: per proof a list of decimal strings or integers;
-    proofs: snarkjs proof.json dicts or the 256-byte form zkwg.prover writes; device: the GPU, or -1 for the host alone; rand: per proof
-    16 bytes, none of them all zero (tests; None draws them from the operating system inside the call)"""
-    from . import _lib
-    lib = _lib.load()
+def _arguments(vkey, publics, proofs):
+    """-> (key, the buffer its ic points into, n, the proofs' bytes, the public inputs' bytes)"""
     key, ic, n_public = _key(vkey)
     n = len(proofs)
     if len(publics) != n:
@@ -103,10 +103,33 @@ def verify_batch(vkey, publics, proofs, device=0, rand=None):
         raise VerifyError(f"every proof needs {n_public} public inputs")
     raw = b"".join(proof_bytes(p) for p in proofs)
     pub = b"".join(_int(x, "public input").to_bytes(32, "little") for p in publics for x in p)
+    return key, ic, n, raw, pub
+
+
+def verify_batch(vkey, publics, proofs, device=0, rand=None):
+    """-> [bool per proof].  vkey: a snarkjs verification_key.json dict; publics: per proof a list of decimal strings or integers;
+    proofs: snarkjs proof.json dicts or the 256-byte form zkwg.prover writes; device: the GPU, or -1 for the host alone; rand: per proof
+    16 bytes, none of them all zero (tests; None draws them from the operating system inside the call)"""
+    from . import _lib
+    lib = _lib.load()
+    key, ic, n, raw, pub = _arguments(vkey, publics, proofs)
     if rand is not None and len(rand) != 16 * n:
         raise VerifyError("rand: 16 bytes per proof")
     ok = (C.c_uint8 * max(1, n))()
     rc = lib.zkwg_groth16_verify_batch(device, C.byref(key), n, raw, pub, None if rand is None else bytes(rand), ok)
+    del ic
+    _call.check(lib, rc, VerifyError)
+    return [bool(v) for v in ok[:n]]
+
+
+def verify_each(vkey, publics, proofs, device=0):
+    """-> [bool per proof], every proof checked on its own (zkwg_groth16_verify_each): the arguments of verify_batch without rand.  The
+    work is three Miller loops and one final exponentiation per proof, whatever share of the proofs is bad."""
+    from . import _lib
+    lib = _lib.load()
+    key, ic, n, raw, pub = _arguments(vkey, publics, proofs)
+    ok = (C.c_uint8 * max(1, n))()
+    rc = lib.zkwg_groth16_verify_each(device, C.byref(key), n, raw, pub, ok)
     del ic
     _call.check(lib, rc, VerifyError)
     return [bool(v) for v in ok[:n]]
@@ -125,19 +148,28 @@ def stats():
     return list(sec), list(cnt)
 
 
+def stats_each():
+    """-> (seconds[6], counts[4]) of this thread's last verify_each (zkwg_groth16_verify_each_stats)"""
+    from . import _lib
+    sec, cnt = (C.c_double * 6)(), (C.c_uint64 * 4)()
+    _lib.load().zkwg_groth16_verify_each_stats(sec, cnt)
+    return list(sec), list(cnt)
+
+
 def main(argv=None):
     ap = argparse.ArgumentParser(prog="python -m zkwg.verify", description="snarkjs groth16 verify")
     ap.add_argument("vkey")
     ap.add_argument("public")
     ap.add_argument("proof")
     ap.add_argument("--device", type=int, default=-1, help="the GPU that runs the Miller loops; -1 (default): the host alone")
+    ap.add_argument("--each", action="store_true", help="check every proof on its own (verify_each): no batch equation, no bisection")
     a = ap.parse_args(argv)
     try:
         vkey, public, proof = (json.load(open(f)) for f in (a.vkey, a.public, a.proof))
         batch = isinstance(proof, list)
         if not isinstance(public, list):
             raise VerifyError("public.json: a list is expected")
-        good = verify_batch(vkey, public if batch else [public], proof if batch else [proof], device=a.device)
+        good = (verify_each if a.each else verify_batch)(vkey, public if batch else [public], proof if batch else [proof], device=a.device)
     except (VerifyError, OSError, ValueError) as e:
         print(f"zkwg.verify: {e}", file=sys.stderr)
         return 2
