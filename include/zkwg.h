@@ -910,6 +910,84 @@ int zkwg_calculate_batch_multi(zkwg_multi_t* m, const uint8_t* packed_inputs, ui
                                uint8_t* out_wtns, uint64_t out_stride, int32_t* status, uint8_t* table,
                                uint64_t max_tile);
 
+/* ---- DKIM verification of raw emails -------------------------------------------------
+ * The step before zkwg_generate_inputs_device: `verifyDKIMSignature` of the reference (packages/helpers/src/dkim/index.ts:36-97)
+ * for a batch of raw messages.  The host parses each message and canonicalises its few hundred bytes of signed header
+ * (zkwg_dkim_parse); the device canonicalises the bodies (zk_dkim_body), hashes bodies and headers (zk_dkim_hash) and checks
+ * bh= and the RSA signature against every candidate key (zk_dkim_verify).  rsa-sha256 only, moduli of 1024 .. 2048 bits,
+ * e = 65537.  No DNS: the caller brings the keys.
+ * Per-email status (zkwg_strerror gives the reference's words; precedence as dkim-verifier.ts:245-335: body hash, key, signature): */
+enum zkwg_dkim_status {
+  ZKWG_DKIM_PASS = 0,
+  ZKWG_DKIM_NOT_FOUND = 101,        /* "DKIM signature not found for domain" D (zkwg_dkim_parsed.d holds D) */
+  ZKWG_DKIM_MULTIPLE_FROM = 102,    /* "Multiple From header in email and domain for verification not specified" */
+  ZKWG_DKIM_NO_KEY = 103,           /* "no key" */
+  ZKWG_DKIM_BODY_HASH = 104,        /* "body hash did not verify" */
+  ZKWG_DKIM_BAD_SIGNATURE = 105,    /* "bad signature" */
+  ZKWG_DKIM_UNSUPPORTED = 106,      /* algorithm other than rsa-sha256, no key of 1024 .. 2048 bits with e = 65537, malformed or missing
+                                       tags (h, bh, b; l= with non-digits; b= longer than 256 bytes), canonical header longer than its slot */
+  ZKWG_DKIM_BODY_DOES_NOT_FIT = 107 /* the canonical body is longer than body_stride */
+};
+typedef struct zkwg_dkim_parsed {
+  int32_t status;                /* PASS, NOT_FOUND, MULTIPLE_FROM or UNSUPPORTED */
+  uint32_t header_len;           /* canonical signed header bytes (also set when they did not fit header_cap) */
+  uint64_t body_offset, body_len;/* the raw body inside the message */
+  uint32_t header_canon, body_canon;   /* 0 relaxed, 1 simple */
+  uint32_t has_l;
+  uint64_t l;                    /* l=, when has_l */
+  uint8_t bh[32];                /* bh= decoded */
+  char bh_b64[48];               /* bh= as text (44 characters) */
+  uint8_t signature[256];        /* b= decoded, big-endian, right-aligned */
+  uint32_t signature_len;
+  char d[256], s[256], a[64], c[64];   /* d= (NOT_FOUND: the domain that was looked for), s=, a=, c= as written */
+  uint64_t body_bound;           /* zkwg_dkim_parse_batch only: no canonical form of the body is longer (body_len + its bare LFs + 2):
+                                    the body_stride that always fits */
+} zkwg_dkim_parsed;
+/* One message: picks the signature of `domain` (NULL or "": of the single From address), writes its canonical signed header
+ * (the fields of h= bottom-up, then the signature field with b= emptied) to header_out[0 .. header_cap) and fills *out.
+ * Returns out->status.  Never reads outside raw[0 .. len).  header_out = NULL: the header is not written (header_cap still bounds it).
+ * zkwg_dkim_parse_batch: the fields of n messages (no headers) on `threads` host threads (0 = the machine's, at most 16) -- what a
+ * caller needs to look the keys up (s=, d=) before zkwg_dkim_verify_batch. */
+int zkwg_dkim_parse(const uint8_t* raw, uint64_t len, const char* domain, uint8_t* header_out, uint32_t header_cap, zkwg_dkim_parsed* out);
+int zkwg_dkim_parse_batch(uint64_t n, const uint8_t* const* emails, const uint64_t* email_len, const char* domain, int32_t threads,
+                          zkwg_dkim_parsed* out);
+
+typedef struct zkwg_dkim_key {
+  uint8_t modulus_be[256];       /* big-endian, right-aligned */
+  uint32_t bits;                 /* of the modulus as the record states it; above 2048 the key is unsupported */
+  uint32_t exponent;
+} zkwg_dkim_key;
+#define ZKWG_DKIM_SKIP_BODY_HASH 1u
+typedef struct zkwg_dkim_verify_args {
+  int32_t device;                /* HIP device, or -1: the same cores on the host */
+  int32_t threads;               /* host threads: for the parser and the packing of the bodies, and for everything with device = -1;
+                                    0 = as many as the machine has, at most 16 */
+  uint64_t n;
+  const uint8_t* const* emails;  /* [n] raw messages */
+  const uint64_t* email_len;     /* [n] */
+  const char* domain;            /* or NULL */
+  const zkwg_dkim_key* keys;     /* the candidate keys of email i: keys[key_first[i] .. key_first[i + 1]), tried in order */
+  const uint32_t* key_first;     /* [n + 1] */
+  uint32_t flags;                /* ZKWG_DKIM_SKIP_BODY_HASH */
+  uint32_t header_stride, body_stride;
+  /* results on the host; every pointer but status may be NULL */
+  int32_t* status;               /* [n] enum zkwg_dkim_status */
+  int32_t* key_index;            /* [n] index among the email's keys of the one that verified, else -1 */
+  uint8_t* headers;              /* [n][header_stride]; bytes beyond a header's length are not written */
+  uint32_t* header_len;          /* [n] */
+  uint8_t* bodies;               /* [n][body_stride]; bytes beyond a body's length are not written */
+  uint32_t* body_len;            /* [n] */
+  uint8_t* body_digest;          /* [n][32] SHA-256 of the canonical body */
+  uint8_t* header_digest;        /* [n][32] SHA-256 of the canonical signed header */
+  zkwg_dkim_parsed* parsed;      /* [n] */
+  /* device >= 0: when given, the filled batch stays on the device (pubkey_be = the key that verified, else the first candidate;
+   * signature_be; body_hash_b64 = bh=), ready for zkwg_generate_inputs_device; release it with zkwg_dkim_batch_free */
+  zkwg_dkim_batch* device_batch;
+  double* seconds;               /* [6] parse, upload, zk_dkim_body, zk_dkim_hash, zk_dkim_verify, download */
+} zkwg_dkim_verify_args;
+int zkwg_dkim_verify_batch(const zkwg_dkim_verify_args* args);
+int zkwg_dkim_batch_free(int device, zkwg_dkim_batch* batch);
+
 #ifdef __cplusplus
 }
 #endif

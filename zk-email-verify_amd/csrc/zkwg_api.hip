@@ -245,6 +245,13 @@ const char* zkwg_strerror(int rc) {
     case 5: return "Not enough memory";
     case 6: return "Input signal array access exceeds the size";
     case ZKWG_ERR_WITNESS_NOT_REDUCED: return "zkwg: a witness value is not below the field order";
+    case ZKWG_DKIM_NOT_FOUND: return "DKIM signature not found for domain";
+    case ZKWG_DKIM_MULTIPLE_FROM: return "Multiple From header in email and domain for verification not specified";
+    case ZKWG_DKIM_NO_KEY: return "no key";
+    case ZKWG_DKIM_BODY_HASH: return "body hash did not verify";
+    case ZKWG_DKIM_BAD_SIGNATURE: return "bad signature";
+    case ZKWG_DKIM_UNSUPPORTED: return "unsupported";
+    case ZKWG_DKIM_BODY_DOES_NOT_FIT: return "body does not fit";
     case ZKWG_RC_BAD_CONFIG: return "zkwg: unsupported circuit configuration";
     case ZKWG_RC_BAD_ARG: return "zkwg: bad argument";
     case ZKWG_RC_NO_DEVICE: return "zkwg: no HIP device (layout-only handle or HIP unavailable)";

@@ -1,6 +1,7 @@
-// The host scaffold of the key-ceremony device calls: what zkwg_{setup,phase2,ptau,ptau_key,verify,pair,fexp}_api.hip (and nothing else) are
-// written with.  Every one of those calls is one-shot -- it allocates its device buffers, synchronises and frees everything before it
-// returns -- so they share: the declarations of the launch wrappers, the sizes of a point, the refusal (fail), one owner of device
+// The host scaffold of the one-shot device calls -- the key ceremony, proof checking and DKIM verification: what
+// zkwg_{setup,phase2,ptau,ptau_key,verify,pair,fexp,dkim}_api.hip (and nothing else) are written with.  Every one of those calls allocates its
+// device buffers, synchronises and frees everything before it returns (zkwg_dkim_verify_batch may hand the batch's buffers to its caller) --
+// so they share: the declarations of the launch wrappers, the sizes of a point, the refusal (fail), one owner of device
 // buffers (DevBufs), the read of the fault flags (zk_read_flags), a stage clock, the per-thread statistics (ZkStats) and the check of
 // the point arguments.  The piece loops themselves stay in their files.  Host only: no kernel includes this.
 #pragma once
@@ -41,6 +42,12 @@ void zk_fexp_ninv_launch(const void* x, const void* y, u32 n, void* out, hipStre
 void zk_fexp_pow_u_launch(const void* g, u32 n, void* out, hipStream_t st);
 void zk_fexp_step_launch(const void* x, const void* y, u32 n, u32 pre_a, u32 pre_b, u32 post, void* out, hipStream_t st);
 void zk_g16_vkx_launch(const void* ic0, const void* terms, u32 n_terms, u32 n, void* g1, hipStream_t st);
+// zkwg_kernels_dkim.hip
+void zk_dkim_body_launch(const void* recs, const void* raw, void* bodies, void* body_len, void* fits, u32 stride, u32 n, hipStream_t st);
+void zk_dkim_hash_launch(const void* recs, const void* bodies, const void* body_len, const void* fits, u32 body_stride, const void* headers,
+                         const void* header_len, u32 header_stride, void* body_digest, void* header_digest, u32 n, hipStream_t st);
+void zk_dkim_verify_launch(const void* recs, const void* keys, const void* fits, const void* body_digest, const void* header_digest, const void* signature_be,
+                           u32 flags, void* status, void* key_index, void* pubkey_be, u32 n, hipStream_t st);
 // zkwg_api.hip
 extern "C" void zk_set_last_error(const char* m);
 

@@ -41,6 +41,30 @@ class DkimBatch(C.Structure):
                 ("selector_len", C.c_uint32)]
 
 
+class DkimParsed(C.Structure):   # zkwg_dkim_parsed
+    _fields_ = [("status", C.c_int32), ("header_len", C.c_uint32), ("body_offset", C.c_uint64), ("body_len", C.c_uint64),
+                ("header_canon", C.c_uint32), ("body_canon", C.c_uint32), ("has_l", C.c_uint32), ("l", C.c_uint64),
+                ("bh", C.c_uint8 * 32), ("bh_b64", C.c_char * 48), ("signature", C.c_uint8 * 256), ("signature_len", C.c_uint32),
+                ("d", C.c_char * 256), ("s", C.c_char * 256), ("a", C.c_char * 64), ("c", C.c_char * 64), ("body_bound", C.c_uint64)]
+
+
+class DkimKey(C.Structure):   # zkwg_dkim_key
+    _fields_ = [("modulus_be", C.c_uint8 * 256), ("bits", C.c_uint32), ("exponent", C.c_uint32)]
+
+
+class DkimVerifyArgs(C.Structure):   # zkwg_dkim_verify_args
+    _fields_ = [("device", C.c_int32), ("threads", C.c_int32), ("n", C.c_uint64), ("emails", C.POINTER(C.c_char_p)),
+                ("email_len", C.POINTER(C.c_uint64)), ("domain", C.c_char_p), ("keys", C.POINTER(DkimKey)),
+                ("key_first", C.POINTER(C.c_uint32)), ("flags", C.c_uint32), ("header_stride", C.c_uint32), ("body_stride", C.c_uint32),
+                ("status", C.c_void_p), ("key_index", C.c_void_p), ("headers", C.c_void_p), ("header_len", C.c_void_p),
+                ("bodies", C.c_void_p), ("body_len", C.c_void_p), ("body_digest", C.c_void_p), ("header_digest", C.c_void_p),
+                ("parsed", C.POINTER(DkimParsed)), ("device_batch", C.POINTER(DkimBatch)), ("seconds", C.POINTER(C.c_double))]
+
+
+(DKIM_PASS, DKIM_NOT_FOUND, DKIM_MULTIPLE_FROM, DKIM_NO_KEY, DKIM_BODY_HASH, DKIM_BAD_SIGNATURE, DKIM_UNSUPPORTED,
+ DKIM_BODY_DOES_NOT_FIT) = 0, 101, 102, 103, 104, 105, 106, 107
+DKIM_SKIP_BODY_HASH = 1
+
 MAIN_EMAIL_VERIFIER, MAIN_SHA256_BYTES, MAIN_RSA_VERIFIER, MAIN_FP_MUL = 0, 1, 2, 3
 (IN_HEADER, IN_BODY, IN_PRECOMPUTED_SHA, IN_PUBKEY, IN_SIGNATURE, IN_MESSAGE,
  IN_HEADER_LEN, IN_BODY_LEN, IN_BODY_HASH_INDEX, IN_HEADER_MASK, IN_BODY_MASK, IN_DECODED_BODY,
@@ -212,6 +236,10 @@ def load():
         "zkwg_calculate_batch_resident": (i32, [vp, vp, u64, vp, vp, u64, u64, vp, vp]),
         "zkwg_resident_placement": (i32, [vp, C.POINTER(C.c_float), i32, C.POINTER(C.c_int)]),
         "zkwg_resident_release": (i32, [vp]),
+        "zkwg_dkim_parse": (i32, [C.c_char_p, u64, C.c_char_p, vp, u32, C.POINTER(DkimParsed)]),
+        "zkwg_dkim_parse_batch": (i32, [u64, C.POINTER(C.c_char_p), C.POINTER(C.c_uint64), C.c_char_p, i32, C.POINTER(DkimParsed)]),
+        "zkwg_dkim_verify_batch": (i32, [C.POINTER(DkimVerifyArgs)]),
+        "zkwg_dkim_batch_free": (i32, [i32, C.POINTER(DkimBatch)]),
     }
     for name, (res, args) in sig.items():
         fn = getattr(lib, name)  # AttributeError if the .so does not export it
@@ -241,4 +269,5 @@ EXPORTS = [
     "zkwg_pairing_check", "zkwg_g2_subgroup_device", "zkwg_point_rlc_device", "zkwg_point_rlc32_device",
     "zkwg_miller_device", "zkwg_fq12_product_device", "zkwg_groth16_verify_batch", "zkwg_groth16_verify_stats",
     "zkwg_final_exp_device", "zkwg_groth16_verify_each", "zkwg_groth16_verify_each_stats",
+    "zkwg_dkim_parse", "zkwg_dkim_parse_batch", "zkwg_dkim_verify_batch", "zkwg_dkim_batch_free",
 ]

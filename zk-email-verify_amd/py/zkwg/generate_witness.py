@@ -3,7 +3,8 @@ generated `generate_witness.js` as the reference documents it (docs/zk-email-doc
 `node generate_witness.js circuit.wasm input.json witness.wtns`).  <circuit> names the circuit by its template
 parameters instead of a WASM file: `EmailVerifier(1024,1536,121,17,0,0,0,0)` or a JSON object / file with the
 keyword arguments of zkwg.Circuit.  An input file holding a list writes <witness>_<i>.wtns per email and exits 1
-if any email failed."""
+if any email failed.  `--eml`: <input> is a raw email; it is verified first (zkwg.dkim, keys from `--keys keys.json`:
+name -> TXT records) and its inputs are generated for the circuit's sizes (zkwg.inputs.generate_email_verifier_inputs)."""
 import json
 import os
 import re
@@ -32,12 +33,26 @@ def circuit_kwargs(arg):
 
 
 def main(argv=None):
-    a = sys.argv[1:] if argv is None else argv
+    a = list(sys.argv[1:] if argv is None else argv)
+    eml = "--eml" in a
+    keys = {}
+    if eml:
+        a.remove("--eml")
+    if "--keys" in a:
+        keys = json.load(open(a.pop(a.index("--keys") + 1)))
+        a.remove("--keys")
     if len(a) < 3:
-        print("Usage: python -m zkwg.generate_witness <circuit> <input.json> <witness.wtns> [device]", file=sys.stderr)
+        print("Usage: python -m zkwg.generate_witness <circuit> <input.json | --eml email.eml --keys keys.json> <witness.wtns> [device]", file=sys.stderr)
         return 2
     c = zkwg.Circuit(device=int(a[3]) if len(a) > 3 else 0, **circuit_kwargs(a[0]))
-    inp = json.load(open(a[1]))
+    if eml:
+        from zkwg import inputs
+        keys = {k: [v] if isinstance(v, str) else v for k, v in keys.items()}
+        inp = inputs.generate_email_verifier_inputs(open(a[1], "rb").read(), {
+            "maxHeadersLength": c.cfg.max_header, "maxBodyLength": c.cfg.max_body, "ignoreBodyHashCheck": bool(c.cfg.ignore_body_hash_check),
+            "removeSoftLineBreaks": bool(c.cfg.remove_soft_line_breaks)}, keys=keys, device=c.device)
+    else:
+        inp = json.load(open(a[1]))
     many = isinstance(inp, list)
     wits, status = c.calculate_batch_host(b"".join(c.pack(x) for x in (inp if many else [inp])))
     wb = c.witness_bytes

@@ -7,6 +7,7 @@ binary-format}.ts of the reference (the `CircuitInput` object is the boundary fo
   to_circom_bigint_bytes          <- binary-format.ts:71-83   toCircomBigIntBytes
   generate_email_verifier_inputs_from_dkim_result
                                   <- input-generators.ts:190-252
+  generate_email_verifier_inputs  <- input-generators.ts:168-181 (the raw email; DKIM by zkwg.dkim)
 """
 import struct
 
@@ -188,3 +189,17 @@ def generate_email_verifier_inputs_from_dkim_result(dkim, max_headers_length=Non
         if enable_body_masking:
             inputs["bodyMask"] = list(body_mask)
     return inputs
+
+
+def generate_email_verifier_inputs(raw_email, params=None, dkim_verification_args=None, keys=None, device=0):
+    """input-generators.ts:168-181: verifyDKIMSignature(rawEmail, domain, enableSanitization), then the function above.
+    `params`: the reference's InputGenerationArgs by their own names (maxHeadersLength, maxBodyLength, ignoreBodyHashCheck,
+    shaPrecomputeSelector, enableHeaderMasking, headerMask, enableBodyMasking, bodyMask, removeSoftLineBreaks);
+    `dkim_verification_args`: domain, enableSanitization; `keys`: see zkwg.dkim (there is no DNS)."""
+    from . import dkim
+    p, a = dict(params or {}), dict(dkim_verification_args or {})
+    result = dkim.verify_dkim_signature(raw_email, a.get("domain") or "", a.get("enableSanitization", True), keys=keys, device=device)
+    return generate_email_verifier_inputs_from_dkim_result(
+        result, p.get("maxHeadersLength"), p.get("maxBodyLength"), bool(p.get("ignoreBodyHashCheck")), p.get("shaPrecomputeSelector"),
+        bool(p.get("enableHeaderMasking")), p.get("headerMask"), bool(p.get("enableBodyMasking")), p.get("bodyMask"),
+        bool(p.get("removeSoftLineBreaks")))

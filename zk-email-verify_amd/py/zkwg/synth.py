@@ -85,6 +85,60 @@ def synthetic_dkim_result(seed, index, body_len=1024, soft_breaks=False, body=No
     return {"headers": headers, "body": body, "bodyHash": bh, "publicKey": key["n"], "signature": sig}
 
 
+def _relaxed_field(raw):
+    """RFC 6376 3.4.2 of one raw header field (no line end after it)"""
+    import re
+    name, _, value = raw.replace(b"\r\n", b"").partition(b":")
+    return name.strip().lower() + b":" + re.sub(rb"[ \t]+", b" ", value).strip()
+
+
+def synthetic_raw_email(seed, index, body_len=1024, canon="relaxed/relaxed", key=None, l=None):
+    """A raw message (.eml bytes) around synthetic_dkim_result(seed, index, body_len): mixed-case field names, folded fields, stray
+    white space, a folded b=, unsigned fields, and in a relaxed body trailing white space, bare LF line ends and trailing empty lines.
+    For canon = "relaxed/relaxed" and the default key its DKIM result (headers, body, bodyHash, publicKey, signature) is exactly
+    synthetic_dkim_result's; the other three c= combinations sign their own canonical forms.  `l`: an l= tag (the body hash then
+    covers the first l canonical bytes)."""
+    import re
+    d = synthetic_dkim_result(seed, index, body_len)
+    rng = random.Random((seed << 21) ^ (index * 2654435761) ^ 0x5bd1)
+    key = key or test_key()
+    hc, bc = canon.split("/")
+    body = d["body"]
+    if bc == "relaxed":
+        raw_body = b"".join(line + rng.choice([b"", b" ", b"\t ", b"  "]) + rng.choice([b"\r\n", b"\r\n", b"\n"]) for line in body.split(b"\r\n")[:-1])
+        raw_body += rng.choice([b"", b"\r\n", b"\r\n \r\n\n"])
+        canon_body = body
+    else:
+        raw_body = body + rng.choice([b"", b"\r\n\r\n", b"\n"])
+        canon_body = body if body else b"\r\n"
+    if l is not None:
+        canon_body = canon_body[:l]
+    bh = base64.b64encode(hashlib.sha256(canon_body).digest()).decode()
+    *fields, sig_line = d["headers"].split(b"\r\n")
+    raw_fields = []
+    for f in fields:
+        name, _, value = f.partition(b":")
+        name = rng.choice([name.upper(), name.title(), name])
+        if b" " in value and rng.random() < 0.7:                      # fold at one of its blanks
+            cut = rng.choice([i for i, ch in enumerate(value) if ch == 32])
+            value = value[:cut] + rng.choice([b"\r\n\t", b" \r\n ", b"\r\n  "]) + value[cut + 1:]
+        raw_fields.append(name + b":" + rng.choice([b" ", b"", b"  ", b"\t"]) + value + rng.choice([b"", b" ", b" \t"]))
+    text = sig_line.partition(b":")[2].decode()
+    text = re.sub(r"c=[^;]*;", f"c={canon};", text)
+    text = re.sub(r"bh=[^;]*;", f"bh={bh};" + (f" l={l};" if l is not None else ""), text)
+    raw_sig = b"DKIM-Signature: " + text.replace("; d=", ";\r\n\td=").replace("; h=", ";\r\n h=").encode()
+    if hc == "relaxed":
+        canon_header = b"".join(_relaxed_field(f) + b"\r\n" for f in raw_fields) + _relaxed_field(raw_sig)
+    else:
+        canon_header = b"".join(f + b"\r\n" for f in raw_fields) + raw_sig
+    sig = pkcs1_sign_digest(key, hashlib.sha256(canon_header).digest())
+    klen = (key["n"].bit_length() + 7) // 8
+    b64 = base64.b64encode(sig.to_bytes(klen, "big")).decode()
+    raw_sig += b"".join((b"\r\n\t " if i else b"") + b64[i:i + 64].encode() for i in range(0, len(b64), 64))
+    order = [raw_sig, b"Received: from nowhere (unsigned)\r\n\tby synth; Sat, 14 Oct 2023 22:09:53 +0300"] + raw_fields + [b"X-Mailer: zkwg synth"]
+    return b"\r\n".join(order) + b"\r\n\r\n" + raw_body
+
+
 def packed_batch(circuit, seed, n, body_len=1024, first_index=0):
     """n packed input records (bytes, circuit.in_stride each) for an EmailVerifier circuit, built
     exactly as generate_email_verifier_inputs_from_dkim_result would (input-generators.ts:190-252)
