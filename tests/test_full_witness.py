@@ -125,6 +125,56 @@ def test_rsa_main_complete_witness_on_the_gpu_and_it_satisfies_the_r1cs():
     assert fv[0] is None and fv[2] is None and fv[1] is not None     # the failing email violates a constraint
 
 
+@pytest.mark.gpu
+def test_rsa_main_full_batches_second_group_and_tails_of_the_descriptor_kernel_on_the_gpu():
+    """zk_expand3_o0 gives a workgroup 16 emails and works through them in batches of 4.  21 emails: one full group of four
+    batches, then a group of one full batch plus a tail of 1; the sub-range [3, 10): one batch plus a tail of 3.  Email 9 is
+    the record with the corrupted message (status 4): its neighbours in the batch must not notice."""
+    import torch
+    import zkwg
+    meta, sym, r1cs = _load(RSA)
+    c = zkwg.Circuit(zkwg.MAIN_RSA_VERIFIER, max_header=0, max_body=0, device=0, sym=sym, sym_alias=meta["alias"], r1cs=r1cs)
+    rec = c.pack(meta["inputs"])
+    from test_rsa_cpu import KAT_MSG
+    bad = c.pack(dict(meta["inputs"], message=[str(KAT_MSG[0] + 1)] + meta["inputs"]["message"][1:]))
+    n, wb = 21, c.witness_bytes
+    dev, st = torch.device("cuda:0"), torch.cuda.current_stream()
+
+    def prepare(recs):
+        k = len(recs) // c.in_stride
+        d_in = torch.frombuffer(bytearray(recs), dtype=torch.uint8).view(k, c.in_stride).to(dev)
+        d_st = torch.zeros(k, dtype=torch.int32, device=dev)
+        d_scr = torch.empty(c.scratch_bytes(k), dtype=torch.uint8, device=dev)
+        c.prepare_device(d_in, k, d_st, d_scr, st)
+        return k, d_in, d_st, d_scr
+
+    def expand(prepared, first, count):
+        k, d_in, _, d_scr = prepared
+        std = torch.full((count * wb,), 0xA5, dtype=torch.uint8, device=dev)
+        mont = torch.full((count * wb,), 0xA5, dtype=torch.uint8, device=dev)
+        c.expand_device(d_in, k, d_scr, first, count, std, st)
+        c.expand_montgomery_device(d_in, k, d_scr, first, count, mont, st)
+        conv = std.clone()
+        zkwg.convert_montgomery_device(conv, count * c.W, True, st)
+        torch.cuda.synchronize()
+        assert torch.equal(mont, conv)          # the fused Montgomery output = expansion, then conversion
+        return std, mont
+
+    batch = prepare(rec * 9 + bad + rec * 11)
+    std, mont = expand(batch, 0, n)
+    assert batch[2].cpu().tolist() == [0] * 9 + [4] + [0] * 11
+    host = std.cpu().numpy().tobytes()
+    for e in range(n):
+        if e != 9:
+            assert hashlib.sha256(host[e * wb:(e + 1) * wb]).hexdigest() == meta["witness_sha256"], e
+    alone = prepare(bad)
+    std1, mont1 = expand(alone, 0, 1)
+    assert alone[2].cpu().tolist() == [4]
+    assert torch.equal(std[9 * wb:10 * wb], std1) and torch.equal(mont[9 * wb:10 * wb], mont1)
+    sub_std, sub_mont = expand(batch, 3, 7)
+    assert torch.equal(sub_std, std[3 * wb:10 * wb]) and torch.equal(sub_mont, mont[3 * wb:10 * wb])
+
+
 STAND_IN = os.path.join(ROOT, "zk-email-verify_amd", "data", "templates", "zk-regex-circom", "circuits", "common", "body_hash_regex.circom")
 
 

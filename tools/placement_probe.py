@@ -25,7 +25,7 @@ def main():
     ap.add_argument("--tile", type=int, default=512)
     ap.add_argument("--reps", type=int, default=4)
     ap.add_argument("--one-block", type=int, default=0, help="1: carve the tiles out of ONE allocation instead of one allocation each")
-    ap.add_argument("--variants", default="", help="comma list of ENV=V+ENV=V handle variants, e.g. ZKWG_XCD_REMAP=0,ZKWG_XCD_REMAP=217+ZKWG_X3_K=2")
+    ap.add_argument("--variants", default="", help="comma list of ENV=V+ENV=V handle variants, e.g. ZKWG_XCD_REMAP=0,ZKWG_XCD_REMAP=217+ZKWG_O0_EMAILS_PER_WG=8")
     ap.add_argument("--out", default=None)
     args = ap.parse_args()
     import torch

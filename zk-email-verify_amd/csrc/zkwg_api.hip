@@ -29,8 +29,6 @@
 #define ZK_MAX_KERNELS 9
 #define ZK_O0_SHORT_ROW 8   // host evaluation of the plan (tests): rows up to this many terms are listed first
 #define ZK_RS_SLOTS 16
-#define ZK_POS_STREAMS 4
-#define ZK_POS_RING 64
 #define ZK_EV_RING 512   // launches whose HIP events are kept for zkwg_timing_summary
 
 struct zkwg_circuit;
@@ -76,12 +74,9 @@ struct zkwg_circuit {
   int host_expand_threads;       // > 0: zkwg_calculate_batch expands on the host (zkwg_set_host_expand)
   u8* hx_img[2]; u64 hx_bytes;   // pinned staging of downloaded images (host expansion)
   int o0_emails_per_wg;          // emails per workgroup of zk_expand3_o0 (ZKWG_O0_EMAILS_PER_WG, default 16)
-  int o0_pipe;                   // zk_expand3_o0 variant (ZKWG_O0_PIPE): 0 plain, 1 one email ahead, 2 (default) batches of 4 emails + short paths for uniform pieces, 3 double-buffered batches
-  int rslb_v;              // zk_rslb_chunks' evaluator variant (ZKWG_RSLB_V = 0..3, zkwg_poseidon29.h)
   u32 pos2_l29_off = 0;    // words: the Poseidon(2) limb table behind the Poseidon(16) one in d_pos_l29
   int rs_merge_lanes = 1;  // zk_rslb_merge1 (one lane per email, limb form) | 4: zk_rslb_merge (ZKWG_RSLB_MERGE_LANES)
   Fr* d_rs_zero = nullptr; // removeSoftLineBreaks: signals + digest of the all-zero chunk (constant chunks, zkwg_kernels_rslb.hip); null: off
-  int x3_k, x3_k_o0;       // slots per thread of zk_expand3 (kept-v1 / sym layouts) and zk_expand3_o0: 1, 2 or 4 (ZKWG_X3_K, ZKWG_X3_K_O0)
   std::vector<ZkSeg> segs;
   hipStream_t own_stream, copy_stream;
   // removeSoftLineBreaks: the serial merge chain (zk_rslb_chain, ~16 waves per 1024 emails, latency-bound)
@@ -91,12 +86,6 @@ struct zkwg_circuit {
   hipEvent_t rs_dep[ZK_RS_SLOTS], rs_done[ZK_RS_SLOTS];
   const void* rs_scr[ZK_RS_SLOTS];
   int rs_next, rs_sync, rs_nside;
-  // zk_poseidon9 (one lane per email: ~3.5 ms of latency, a handful of wavefronts) can run beside the
-  // other prepare kernels on a low-priority side stream, joined at the end of prepare (off by default).
-  hipStream_t pos_stream[ZK_POS_STREAMS];
-  hipEvent_t pos_dep[ZK_POS_RING], pos_done[ZK_POS_RING];
-  u64 pos_calls;
-  int pos_side;   // 1: fork zk_poseidon9 onto a side stream (ZKWG_POS_SIDE=1); default 0 = caller's stream
   int pos_lane;   // 1: the lane-per-email zk_poseidon9 of round 2 instead of zk_poseidon9_g16 (ZKWG_POS_LANE=1)
   int pos_wave_below;   // batches below this many emails use the wavefront-per-email kernel (ZKWG_POS_WAVE_BELOW, default 1024)
   u32 xcd_remap;  // zk_expand workgroup -> portion mapping (ZKWG_XCD_REMAP)
@@ -220,7 +209,7 @@ static bool upload_o0(zkwg_circuit* c, ZkO0Tables& T, ZkO0Dev& O, u64 W, bool ke
   up(T.gen_seg.data(), T.gen_seg.size() * 4, (void**)&O.gen_seg);
   up(T.gen_r.data(), T.gen_r.size() * 4, (void**)&O.gen_r);
   O.n_gen = (u32)T.gen_seg.size(); O.gen_base = T.gen_base;
-  O.W = W; O.nportions = (u32)((W + 256u * c->x3_k_o0 - 1) / (256u * c->x3_k_o0)); O.small_base = T.small_base; O.fr_base = T.fr_base;
+  O.W = W; O.nportions = (u32)((W + 256u * ZK_X3_SLOTS_O0 - 1) / (256u * ZK_X3_SLOTS_O0)); O.small_base = T.small_base; O.fr_base = T.fr_base;
   O.emails_per_wg = (u32)c->o0_emails_per_wg;
   O.n_fr_groups = (u32)T.n_fr();   // (field rows are never chained: one group each)
   if (ok && !keep_host) { ZkO0Tables keep; keep.small_base = T.small_base; keep.fr_base = T.fr_base; keep.gen_base = T.gen_base; keep.n_alias = T.n_alias; keep.n_const = T.n_const; std::swap(T, keep); }
@@ -275,14 +264,9 @@ static int create_impl(const zkwg_config* cfg_in, int device, const char* sym_te
   zkwg_circuit* c = new zkwg_circuit();
   c->cfg = *cfg;
   c->device = -1;
-  // tuning knobs (DESIGN.md "zk_expand geometry"): slots per workgroup and threads per workgroup
-  auto pick_k = [](const char* name, int dflt, bool k8 = false) { const char* v = getenv(name); const int k = v ? atoi(v) : dflt; return (k == 1 || k == 2 || k == 4 || (k8 && k == 8)) ? k : dflt; };
-  { const char* v = getenv("ZKWG_RSLB_V"); c->rslb_v = v ? (atoi(v) & 7) : 6; }
+  // tuning knobs
   { const char* v = getenv("ZKWG_RSLB_MERGE_LANES"); c->rs_merge_lanes = v && atoi(v) == 4 ? 4 : 1; }
-  c->x3_k = pick_k("ZKWG_X3_K", 4, true);
-  c->x3_k_o0 = pick_k("ZKWG_X3_K_O0", 1);   // (round 4: 8 KiB pieces, 53 VGPRs = 8 wavefronts per SIMD, software-pipelined over the group's emails)
   c->o0_emails_per_wg = getenv("ZKWG_O0_EMAILS_PER_WG") ? std::max(1, atoi(getenv("ZKWG_O0_EMAILS_PER_WG"))) : 16;
-  c->o0_pipe = getenv("ZKWG_O0_PIPE") ? atoi(getenv("ZKWG_O0_PIPE")) : 2;
   c->xcd_remap = getenv("ZKWG_XCD_REMAP") ? (u32)atoi(getenv("ZKWG_XCD_REMAP")) : 1u;
   c->rsa_wgs_per_cu = 0;
   if (const char* v = getenv("ZKWG_RSA_WGS_PER_CU")) c->rsa_wgs_per_cu = atoi(v);
@@ -451,7 +435,7 @@ static int create_impl(const zkwg_config* cfg_in, int device, const char* sym_te
               hipMalloc((void**)&c->d_segs, c->segs.size() * sizeof(ZkSeg)) == hipSuccess;
     {
       std::vector<ZkPortionEntry> ent;
-      zk_build_entries(c->s.W, c->segs, ent, 256u * (u32)c->x3_k);
+      zk_build_entries(c->s.W, c->segs, ent, 256u * ZK_X3_SLOTS);
       c->n_ent = (u32)ent.size();
       ok = ok && hipMalloc((void**)&c->d_ent, ent.size() * sizeof(ZkPortionEntry)) == hipSuccess &&
            hipMemcpy(c->d_ent, ent.data(), ent.size() * sizeof(ZkPortionEntry), hipMemcpyHostToDevice) == hipSuccess;
@@ -565,19 +549,8 @@ static int create_impl(const zkwg_config* cfg_in, int device, const char* sym_te
       c->rs_sync = getenv("ZKWG_RSLB_SYNC") ? atoi(getenv("ZKWG_RSLB_SYNC")) : 0;
       c->rs_nside = getenv("ZKWG_RSLB_SIDE_STREAMS") ? std::min(ZK_RS_SLOTS, std::max(1, atoi(getenv("ZKWG_RSLB_SIDE_STREAMS")))) : 4;
     }
-    {
-      int prio_lo = 0, prio_hi = 0;
-      hipDeviceGetStreamPriorityRange(&prio_lo, &prio_hi);
-      for (int i = 0; i < ZK_POS_STREAMS; ++i) hipStreamCreateWithPriority(&c->pos_stream[i], hipStreamNonBlocking, prio_lo);
-      for (int i = 0; i < ZK_POS_RING; ++i) {
-        hipEventCreateWithFlags(&c->pos_dep[i], hipEventDisableTiming);
-        hipEventCreateWithFlags(&c->pos_done[i], hipEventDisableTiming);
-      }
-      c->pos_calls = 0;
-      c->pos_side = getenv("ZKWG_POS_SIDE") ? atoi(getenv("ZKWG_POS_SIDE")) : 0;   // measured: inline is faster in the pipeline
-      c->pos_lane = getenv("ZKWG_POS_LANE") ? atoi(getenv("ZKWG_POS_LANE")) : 0;
-      c->pos_wave_below = getenv("ZKWG_POS_WAVE_BELOW") ? atoi(getenv("ZKWG_POS_WAVE_BELOW")) : 1024;
-    }
+    c->pos_lane = getenv("ZKWG_POS_LANE") ? atoi(getenv("ZKWG_POS_LANE")) : 0;
+    c->pos_wave_below = getenv("ZKWG_POS_WAVE_BELOW") ? atoi(getenv("ZKWG_POS_WAVE_BELOW")) : 1024;
     for (int i = 0; i < 2; ++i) { hipEventCreateWithFlags(&c->hb_done[i], hipEventDisableTiming); hipEventCreateWithFlags(&c->hb_copied[i], hipEventDisableTiming); }
     for (int r = 0; r < ZK_EV_RING; ++r) {
       for (int i = 0; i < 2; ++i) hipEventCreate(&c->ev[r][i]);
@@ -719,8 +692,6 @@ void zkwg_circuit_destroy(zkwg_circuit_t* c) {
     for (int i = 0; i < 2; ++i) { hipEventDestroy(c->hb_done[i]); hipEventDestroy(c->hb_copied[i]); if (c->hx_img[i]) hipHostFree(c->hx_img[i]); }
     hipStreamDestroy(c->copy_stream);
     hipStreamDestroy(c->own_stream);
-    for (int i = 0; i < ZK_POS_STREAMS; ++i) { hipStreamSynchronize(c->pos_stream[i]); hipStreamDestroy(c->pos_stream[i]); }
-    for (int i = 0; i < ZK_POS_RING; ++i) { hipEventDestroy(c->pos_dep[i]); hipEventDestroy(c->pos_done[i]); }
     if (c->s.rslb) {
       for (int i = 0; i < ZK_RS_SLOTS; ++i) {
         hipStreamSynchronize(c->side_stream[i]);
@@ -982,20 +953,6 @@ int zkwg_prepare_device(zkwg_circuit_t* c, const void* d_in, uint64_t n, void* d
   hipEvent_t* evs = c->pev[c->prep_launches % ZK_EV_RING];
   const u32 pm = c->prep_mask;
   const bool pos9 = s.rsa.present && s.main_kind == ZKWG_MAIN_EMAIL_VERIFIER && (pm & 32u);
-  int pos_slot = -1;
-  if (pos9 && c->pos_side) {
-    // fork: zk_poseidon9 only reads the input record; it overlaps the SHA / regex / RSA kernels (with timing
-    // on, its entry measures the time the caller's stream waits at the join, i.e. the exposed latency)
-    pos_slot = (int)(c->pos_calls % ZK_POS_RING);
-    hipStream_t ps = c->pos_stream[c->pos_calls % ZK_POS_STREAMS];
-    c->pos_calls++;
-    hipEventRecord(c->pos_dep[pos_slot], st);
-    hipStreamWaitEvent(ps, c->pos_dep[pos_slot], 0);
-    if ((int)ne < c->pos_wave_below) hipLaunchKernelGGL(zk_poseidon9_wave, dim3(ne), dim3(64), 0, ps, s, B);
-    else if (c->pos_lane) hipLaunchKernelGGL(zk_poseidon9, dim3((ne + 63) / 64), dim3(64), 0, ps, s, B);
-    else hipLaunchKernelGGL(zk_poseidon9_g16, dim3((ne + 3) / 4), dim3(64), 0, ps, s, B);
-    hipEventRecord(c->pos_done[pos_slot], ps);
-  }
   if (tm) hipEventRecord(evs[ki], st);
   if (s.nframes && (pm & 1u)) {
     u32 threads = ne * s.nframes;
@@ -1032,13 +989,12 @@ int zkwg_prepare_device(zkwg_circuit_t* c, const void* d_in, uint64_t n, void* d
   }
   if (s.fpg.present && (pm & 16u)) hipLaunchKernelGGL(zk_fpmul_small, dim3((ne + 63) / 64), dim3(64), 0, st, s, B);   // (timed in zk_rsa's slot)
   if (tm) hipEventRecord(evs[++ki], st);
-  if (pos9 && pos_slot < 0) {
+  if (pos9) {
     // one lane per email once the batch supplies >= 16 wavefronts of them; one wavefront per email below
     if ((int)ne < c->pos_wave_below) hipLaunchKernelGGL(zk_poseidon9_wave, dim3(ne), dim3(64), 0, st, s, B);
     else if (c->pos_lane) hipLaunchKernelGGL(zk_poseidon9, dim3((ne + 63) / 64), dim3(64), 0, st, s, B);
     else hipLaunchKernelGGL(zk_poseidon9_g16, dim3((ne + 3) / 4), dim3(64), 0, st, s, B);
   }
-  if (pos_slot >= 0) hipStreamWaitEvent(st, c->pos_done[pos_slot], 0);   // join
   if (s.rslb) {
     // removeSoftLineBreaks: chunk hashes (one lane per 16-byte chunk), then the serial merge chain + scans
     if (tm) hipEventRecord(evs[++ki], st);
@@ -1050,16 +1006,7 @@ int zkwg_prepare_device(zkwg_circuit_t* c, const void* d_in, uint64_t n, void* d
         hipLaunchKernelGGL(zk_rslb_classify, dim3((u32)((units + 255) / 256)), dim3(256), 0, st, s, B);
         hipLaunchKernelGGL(zk_rslb_fill_const, dim3(8192), dim3(64), 0, st, s, B);
       }
-      switch (c->rslb_v) {
-        case 1: hipLaunchKernelGGL(zk_rslb_chunks_v1, g, dim3(64), 0, st, s, B); break;
-        case 2: hipLaunchKernelGGL(zk_rslb_chunks_v2, g, dim3(64), 0, st, s, B); break;
-        case 3: hipLaunchKernelGGL(zk_rslb_chunks_v3, g, dim3(64), 0, st, s, B); break;
-        case 4: hipLaunchKernelGGL(zk_rslb_chunks_v4, g, dim3(64), 0, st, s, B); break;
-        case 5: hipLaunchKernelGGL(zk_rslb_chunks_v5, g, dim3(64), 0, st, s, B); break;
-        case 6: hipLaunchKernelGGL(zk_rslb_chunks_v6, g, dim3(64), 0, st, s, B); break;
-        case 7: hipLaunchKernelGGL(zk_rslb_chunks_v7, g, dim3(64), 0, st, s, B); break;
-        default: hipLaunchKernelGGL(zk_rslb_chunks_v0, g, dim3(64), 0, st, s, B); break;
-      }
+      hipLaunchKernelGGL(zk_rslb_chunks, g, dim3(64), 0, st, s, B);
     }
     if (tm) hipEventRecord(evs[++ki], st);
     if (c->rs_sync) {
@@ -1159,12 +1106,7 @@ static int expand_impl(zkwg_circuit_t* c, const void* d_in, uint64_t n, const vo
       if (units > 0x7fffffffull) return ZKWG_RC_BAD_ARG;
       if (mont) hipLaunchKernelGGL(zk_image_to_mont, dim3((u32)((conv + 255) / 256)), dim3(256), 0, st, A);
       const dim3 g3((u32)units), b3(256);
-#define ZK_LAUNCH_O0(K) do { if (c->o0_pipe) { if (mont) hipLaunchKernelGGL(zk_expand3_o0p_mont_k##K, g3, b3, 0, st, A, O); else hipLaunchKernelGGL(zk_expand3_o0p_k##K, g3, b3, 0, st, A, O); } \
-                             else { if (mont) hipLaunchKernelGGL(zk_expand3_o0_mont_k##K, g3, b3, 0, st, A, O); else hipLaunchKernelGGL(zk_expand3_o0_k##K, g3, b3, 0, st, A, O); } } while (0)
-      if (c->x3_k_o0 == 1 && c->o0_pipe == 2) { if (mont) hipLaunchKernelGGL(zk_expand3_o0b_mont_k1, g3, b3, 0, st, A, O); else hipLaunchKernelGGL(zk_expand3_o0b_k1, g3, b3, 0, st, A, O); }
-      else if (c->x3_k_o0 == 1 && c->o0_pipe == 3) { if (mont) hipLaunchKernelGGL(zk_expand3_o0c_mont_k1, g3, b3, 0, st, A, O); else hipLaunchKernelGGL(zk_expand3_o0c_k1, g3, b3, 0, st, A, O); }
-      else if (c->x3_k_o0 == 1) ZK_LAUNCH_O0(1); else if (c->x3_k_o0 == 2) ZK_LAUNCH_O0(2); else ZK_LAUNCH_O0(4);
-#undef ZK_LAUNCH_O0
+      hipLaunchKernelGGL(mont ? zk_expand3_o0_mont : zk_expand3_o0, g3, b3, 0, st, A, O);
       continue;
     }
     {
@@ -1173,9 +1115,7 @@ static int expand_impl(zkwg_circuit_t* c, const void* d_in, uint64_t n, const vo
       if (units3 > 0x7fffffffull) return ZKWG_RC_BAD_ARG;
       if (mont) hipLaunchKernelGGL(zk_image_to_mont, dim3((u32)((conv + 255) / 256)), dim3(256), 0, st, A);
       const dim3 g3((u32)units3), b3(256);
-#define ZK_LAUNCH_X3(K) do { if (mont) hipLaunchKernelGGL(zk_expand3_mont_k##K, g3, b3, 0, st, A); else hipLaunchKernelGGL(zk_expand3_k##K, g3, b3, 0, st, A); } while (0)
-      if (c->x3_k == 1) ZK_LAUNCH_X3(1); else if (c->x3_k == 2) ZK_LAUNCH_X3(2); else if (c->x3_k == 8) ZK_LAUNCH_X3(8); else ZK_LAUNCH_X3(4);
-#undef ZK_LAUNCH_X3
+      hipLaunchKernelGGL(mont ? zk_expand3_mont : zk_expand3, g3, b3, 0, st, A);
     }
   }
   if (tm) { hipEventRecord(evs[1], st); c->ev_valid = true; c->launches++; }

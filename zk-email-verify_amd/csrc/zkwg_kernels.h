@@ -14,14 +14,7 @@ __global__ void zk_poseidon9_g16(ZkSched s, ZkBufs B);
 __global__ void zk_misc_ev(ZkSched s, ZkBufs B);     // zkwg_kernels_misc.hip
 __global__ void zk_net_eval(ZkSched s, ZkBufs B);    // zkwg_kernels_net.hip
 __global__ void zk_net_scan(ZkSched s, ZkBufs B);
-__global__ void zk_rslb_chunks_v0(ZkSched s, ZkBufs B); // zkwg_kernels_rslb.hip (v0..v3: evaluator variants, zkwg_poseidon29.h)
-__global__ void zk_rslb_chunks_v1(ZkSched s, ZkBufs B);
-__global__ void zk_rslb_chunks_v2(ZkSched s, ZkBufs B);
-__global__ void zk_rslb_chunks_v3(ZkSched s, ZkBufs B);
-__global__ void zk_rslb_chunks_v4(ZkSched s, ZkBufs B);
-__global__ void zk_rslb_chunks_v5(ZkSched s, ZkBufs B);
-__global__ void zk_rslb_chunks_v6(ZkSched s, ZkBufs B);
-__global__ void zk_rslb_chunks_v7(ZkSched s, ZkBufs B);
+__global__ void zk_rslb_chunks(ZkSched s, ZkBufs B); // zkwg_kernels_rslb.hip (evaluator: zkwg_poseidon29.h, V = 6)
 #include "zkwg_rslb_wave.h"   // ZK_RS_MERGE_LANES
 __global__ void zk_rslb_merge(ZkSched s, ZkBufs B);
 __global__ void zk_rslb_merge1(ZkSched s, ZkBufs B);     // the same chain, one lane per email in limb form
@@ -32,16 +25,12 @@ __global__ void zk_r1cs_check(const u64* row_ptr, const u32* wire, const Fr* coe
                               const u8* wit, u64 stride, unsigned long long* first_bad);  // zkwg_kernels_r1cs.hip
 __global__ void zk_r1cs_eval(const u64* row_ptr, const u32* wire, const Fr* coef, const u8* kind, u32 m, const u8* wit, u64 stride,
                              u8* out, u64 out_stride, int mont);  // zkwg_kernels_r1cs.hip
-// zkwg_kernels_expand3.hip: one piece of 256 K slots per workgroup (K = 1, 2, 4), standard / Montgomery form, kept-v1 / numbered circuits
-#define ZK_X3_DECL(K) \
-  __global__ void zk_expand3_k##K(ZkX3 A); __global__ void zk_expand3_mont_k##K(ZkX3 A); \
-  __global__ void zk_expand3_o0_k##K(ZkX3 A, ZkO0Dev O); __global__ void zk_expand3_o0_mont_k##K(ZkX3 A, ZkO0Dev O); \
-  __global__ void zk_expand3_o0p_k##K(ZkX3 A, ZkO0Dev O); __global__ void zk_expand3_o0p_mont_k##K(ZkX3 A, ZkO0Dev O);
-ZK_X3_DECL(1) ZK_X3_DECL(2) ZK_X3_DECL(4)
-__global__ void zk_expand3_k8(ZkX3 A); __global__ void zk_expand3_mont_k8(ZkX3 A);
+// zkwg_kernels_expand3.hip: one piece of 256 K slots per workgroup, standard / Montgomery form; K slots per lane:
+#define ZK_X3_SLOTS 4      // kept-v1 / `.sym` layouts (32 KiB pieces)
+#define ZK_X3_SLOTS_O0 1   // numbered circuits and A.w | B.w | C.w, from per-wire descriptors (8 KiB pieces, emails in batches of 4)
+__global__ void zk_expand3(ZkX3 A); __global__ void zk_expand3_mont(ZkX3 A);
+__global__ void zk_expand3_o0(ZkX3 A, ZkO0Dev O); __global__ void zk_expand3_o0_mont(ZkX3 A, ZkO0Dev O);
 __global__ void zk_image_to_mont(ZkX3 A);
-__global__ void zk_expand3_o0b_k1(ZkX3 A, ZkO0Dev O); __global__ void zk_expand3_o0b_mont_k1(ZkX3 A, ZkO0Dev O);
-__global__ void zk_expand3_o0c_k1(ZkX3 A, ZkO0Dev O); __global__ void zk_expand3_o0c_mont_k1(ZkX3 A, ZkO0Dev O);
 __global__ void zk_o0_rows_small(ZkX3 A, ZkO0Dev O);
 __global__ void zk_o0_chains_small(ZkX3 A, ZkO0Dev O);
 __global__ void zk_o0_generic(ZkX3 A, ZkO0Dev O);

@@ -17,8 +17,9 @@
 // State in LDS as 9 x 29-bit limbs, limb-major (element j, limb l of lane t at st[(l * 17 + j) * 64 + t]: every access is one
 // conflict-free 32-bit word per lane); the dense mixes copy it into registers.  The whole permutation runs in limb form
 // (zkwg_poseidon29.h); only the 612 emitted S-box signals and the digest are packed into 4 x 64-bit words.
-template <int V>
-__device__ __forceinline__ void zk_rslb_chunks_body(const ZkSched& s, const ZkBufs& B) {
+// Evaluator variant 6 (zkwg_poseidon29.h: two state elements per loop iteration, dense mixes through the staging area): 124 registers
+// instead of the 446 of a register copy of the state, so zk_expand keeps six wavefronts per SIMD beside it.
+__global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(1, 1))) void zk_rslb_chunks(ZkSched s, ZkBufs B) {
   __shared__ u32 st[9 * 17 * 64];
   const u32 lane = threadIdx.x;
   u64 unit = (u64)blockIdx.x * 64 + lane;
@@ -39,21 +40,9 @@ __device__ __forceinline__ void zk_rslb_chunks_body(const ZkSched& s, const ZkBu
     for (u32 j = 0; j < 17; ++j) stl[(l * 17 + j) * 64] = (l == 0 && j > 0) ? ((w[(j - 1) >> 2] >> (8 * ((j - 1) & 3))) & 255u) : 0u;
   }
   Fr* frv = B.frv + (u64)e * s.img_fr;
-  const Fr h = zk_poseidon29<17, V>(stl, 64, 17 * 64, B.pos16_l29, 68, frv + s.f_rs_hash + zk_rs_chunk_off(c), B.rs_stage + unit, (size_t)B.rs_units);
+  const Fr h = zk_poseidon29<17, 6>(stl, 64, 17 * 64, B.pos16_l29, 68, frv + s.f_rs_hash + zk_rs_chunk_off(c), B.rs_stage + unit, (size_t)B.rs_units);
   frv[s.f_rs_chunk + c] = h;
 }
-
-// V = evaluator variant (zkwg_poseidon29.h): which of the four runs is ZKWG_RSLB_V's / the measured default's business (zkwg_api.hip)
-#define ZK_RSLB_CHUNKS(V) \
-  __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(1, 1))) void zk_rslb_chunks_v##V(ZkSched s, ZkBufs B) { zk_rslb_chunks_body<V>(s, B); }
-ZK_RSLB_CHUNKS(0)
-ZK_RSLB_CHUNKS(1)
-ZK_RSLB_CHUNKS(2)
-ZK_RSLB_CHUNKS(3)
-ZK_RSLB_CHUNKS(4)
-ZK_RSLB_CHUNKS(5)
-ZK_RSLB_CHUNKS(6)
-ZK_RSLB_CHUNKS(7)
 
 // Constant chunks.  Both halves of the hashed string are zero-padded to maxBody (the encoded body behind its SHA padding, the decoded body
 // behind its last byte), so a third of the chunks of a 1 KB body at maxBody = 1536 -- more for shorter bodies -- are sixteen zero bytes, and

@@ -148,39 +148,6 @@ ZK_HD void zk_l29_mul(u32 (&r)[9], const u32 (&a)[9], BP b) {
 #pragma unroll
   for (int i = 0; i < 9; ++i) r[i] = o[i];
 }
-// the same product with the multiply-adds of a row independent of each other (operand scanning into 17 column sums, then a row-wise
-// reduction): ~290 instructions instead of ~215, but 9 multiply-adds in flight instead of one dependent chain -- for a kernel that
-// runs one wavefront per SIMD
-template <class BP>
-ZK_HD void zk_l29_mul_rows(u32 (&r)[9], const u32 (&a)[9], BP b) {
-  const u32 P[9] = {0x10000001u, 0x1f0fac9fu, 0x0e5c2450u, 0x07d090f3u, 0x1585d283u, 0x02db40c0u, 0x00a6e141u, 0x0e5c2634u, 0x0030644eu};
-  u64 c[18];
-#pragma unroll
-  for (int i = 0; i < 18; ++i) c[i] = 0;
-#pragma unroll
-  for (int i = 0; i < 9; ++i) {
-#pragma unroll
-    for (int k = 0; k < 9; ++k) c[i + k] += (u64)a[i] * b[k];
-  }
-#pragma unroll
-  for (int i = 0; i < 9; ++i) {
-    const u32 m = ((u32)c[i] * ZK_P29_N0) & ZK_P29_M;
-#pragma unroll
-    for (int k = 0; k < 9; ++k) c[i + k] += (u64)m * P[k];
-    c[i + 1] += c[i] >> 29;
-  }
-#pragma unroll
-  for (int k = 9; k < 17; ++k) {
-    r[k - 9] = (u32)c[k] & ZK_P29_M;
-    c[k + 1] += c[k] >> 29;
-  }
-  r[8] = (u32)c[17];
-}
-template <int V, class BP>
-ZK_HD void zk_l29_mulv(u32 (&r)[9], const u32 (&a)[9], BP b) {
-  if (V & 1) zk_l29_mul_rows(r, a, b);
-  else zk_l29_mul(r, a, b);
-}
 // r = a + b, normalised (the top limb takes what is left)
 template <class BP>
 ZK_HD void zk_l29_add(u32 (&r)[9], const u32 (&a)[9], BP b) {
@@ -232,15 +199,14 @@ ZK_HD void zk_l29_from_fr(const Fr& x, u32 (&l)[9]) {
 }
 
 // x -> x^5; emits (x^5, x^2, x^4) canonical.  2^522 mod r = the factor that puts a value into 2^261-Montgomery form.
-template <int V>
 ZK_HD void zk_p29_sbox(u32 (&x)[9], Fr* emit) {
   const u32 RR[9] = {0x05b69bd4u, 0x06170a5au, 0x020cddceu, 0x1db6310bu, 0x0e54d0ffu, 0x1cf855e3u, 0x1c15e103u, 0x07d09161u, 0x000a054au};
   u32 xm[9], in2[9], t[9], in4[9];
-  zk_l29_mulv<V>(xm, x, RR);
-  zk_l29_mulv<V>(in2, xm, x);
-  zk_l29_mulv<V>(t, in2, RR);
-  zk_l29_mulv<V>(in4, t, in2);
-  zk_l29_mulv<V>(x, xm, in4);
+  zk_l29_mul(xm, x, RR);
+  zk_l29_mul(in2, xm, x);
+  zk_l29_mul(t, in2, RR);
+  zk_l29_mul(in4, t, in2);
+  zk_l29_mul(x, xm, in4);
   emit[0] = zk_l29_to_fr(x);
   emit[1] = zk_l29_to_fr(in2);
   emit[2] = zk_l29_to_fr(in4);
@@ -335,9 +301,9 @@ ZK_HD void zk_p29_densev(u32* st, const u32 js, const u32 ls, ZkTab29 mat, const
 
 // One permutation.  st: T state elements in limb form (element j, limb l at st[l * ls + j * js]; values < 2^29 on entry, element 0 =
 // capacity); emit: 3 * (8T + rp) Fr, Sigma signals in component order (sigmaF[8][T], sigmaP[rp]).  Returns out[0] (canonical).
-// V: bit 0 = row-wise products (zk_l29_mul_rows), bit 1 = two state elements per loop iteration (two independent chains of products
-// for the scheduler to interleave), bit 2 = dense mixes through `stage` (zk_p29_dense_lean; stage = 153 words with stride ss, unused
-// otherwise).  Same values either way; which is faster is a measurement (zk_rslb_chunks).
+// V: bit 1 (2) = two state elements per loop iteration (two independent chains of products for the scheduler to interleave), bit 2
+// (4) = dense mixes through `stage` (zk_p29_dense_lean; stage = 153 words with stride ss, unused otherwise).  Same values either
+// way; which is faster was a measurement: zk_rslb_chunks runs 6, zk_rslb_merge1 2, the host 0.
 template <int T, int V = 0>
 ZK_HD Fr zk_poseidon29(u32* st, const u32 js, const u32 ls, const u32* tab_, const u32 rp, Fr* emit, u32* stage = nullptr, const size_t ss = 0) {
   ZkTab29 cF = ZK_TAB29(tab_);
@@ -366,7 +332,7 @@ ZK_HD Fr zk_poseidon29(u32* st, const u32 js, const u32 ls, const u32* tab_, con
         ZkTab29 pk = P + (size_t)k * T * 27;
         u32 y0[9];
         zk_l29_add(y0, u0, pk);
-        zk_p29_sbox<V>(y0, emit + 3 * (8 * T + k));
+        zk_p29_sbox(y0, emit + 3 * (8 * T + k));
         ZkW29 w;
         zk_w29_zero(w);
         zk_w29_mac(w, y0, pk + 9);
@@ -381,8 +347,8 @@ ZK_HD Fr zk_poseidon29(u32* st, const u32 js, const u32 ls, const u32* tab_, con
             zk_w29_mac(w, ua, pj + 9);
             zk_w29_mac(w, ub, pj + 36);
             if ((j & 3u) == 3u) zk_w29_carry(w);       // j = 1, 3, 5 ...: every second pair -> at most 5 multiply-accumulates apart
-            zk_l29_mulv<V>(pa, y0, pj + 18);
-            zk_l29_mulv<V>(pb, y0, pj + 45);
+            zk_l29_mul(pa, y0, pj + 18);
+            zk_l29_mul(pb, y0, pj + 45);
             zk_l29_add3(ua, ua, pa, pj + T * 27);
             zk_l29_add3(ub, ub, pb, pj + T * 27 + 27);
 #pragma unroll
@@ -397,7 +363,7 @@ ZK_HD Fr zk_poseidon29(u32* st, const u32 js, const u32 ls, const u32* tab_, con
           for (int l = 0; l < 9; ++l) uj[l] = st[l * ls + j * js];
           zk_w29_mac(w, uj, pj + 9);
           if ((j & 3u) == 3u) zk_w29_carry(w);
-          zk_l29_mulv<V>(p, y0, pj + 18);
+          zk_l29_mul(p, y0, pj + 18);
           zk_l29_add3(uj, uj, p, pj + T * 27);
 #pragma unroll
           for (int l = 0; l < 9; ++l) st[l * ls + j * js] = uj[l];
@@ -420,8 +386,8 @@ ZK_HD Fr zk_poseidon29(u32* st, const u32 js, const u32 ls, const u32* tab_, con
           for (int l = 0; l < 9; ++l) { xa[l] = st[l * ls + j * js]; xb[l] = st[l * ls + (j + 1) * js]; }
           zk_l29_add(xa, xa, c + 9 * j);
           zk_l29_add(xb, xb, c + 9 * j + 9);
-          zk_p29_sbox<V>(xa, emit + 3 * ((half * 4 + r) * T + j));
-          zk_p29_sbox<V>(xb, emit + 3 * ((half * 4 + r) * T + j + 1));
+          zk_p29_sbox(xa, emit + 3 * ((half * 4 + r) * T + j));
+          zk_p29_sbox(xb, emit + 3 * ((half * 4 + r) * T + j + 1));
 #pragma unroll
           for (int l = 0; l < 9; ++l) { st[l * ls + j * js] = xa[l]; st[l * ls + (j + 1) * js] = xb[l]; }
         }
@@ -432,7 +398,7 @@ ZK_HD Fr zk_poseidon29(u32* st, const u32 js, const u32 ls, const u32* tab_, con
 #pragma unroll
         for (int l = 0; l < 9; ++l) x[l] = st[l * ls + j * js];
         zk_l29_add(x, x, c + 9 * j);
-        zk_p29_sbox<V>(x, emit + 3 * ((half * 4 + r) * T + j));
+        zk_p29_sbox(x, emit + 3 * ((half * 4 + r) * T + j));
 #pragma unroll
         for (int l = 0; l < 9; ++l) st[l * ls + j * js] = x[l];
       }

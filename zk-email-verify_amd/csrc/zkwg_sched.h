@@ -114,7 +114,7 @@ ZK_HD u32 zk_seg_period(const ZkSeg& g) {
   }
 }
 
-// zk_expand works in pieces of 256 K slots (K = 1, 2, 4: 8 K KiB of output), one per workgroup.  One table entry per piece:
+// zk_expand works in pieces of 256 K slots (K = ZK_X3_SLOTS = 4: 32 KiB of output), one per workgroup.  One table entry per piece:
 // a piece inside a single segment carries that segment's parameters (type < ZSEG_NTYPES) and the logical index of its
 // first slot; a piece that straddles segments (type = ZSEG_NTYPES) names the first segment to look at.
 struct ZkPortionEntry {
