@@ -58,7 +58,7 @@ extern "C" {
  * zkwg_scratch_bytes includes the Montgomery-copy area (and, round 5, 612 bytes per 16-byte body chunk of staging for the
  * removeSoftLineBreaks chunk hashes, behind the image arrays); zkwg_segment.pad is kernel-private.
  * Added since without breaking 2: zkwg_expand_host / zkwg_set_host_expand, zkwg_circuit_attach_r1cs / zkwg_expand_abc_device /
- * zkwg_expand_abc_host / zkwg_abc_bytes, ZKWG_MAIN_FP_MUL. */
+ * zkwg_expand_abc_host / zkwg_abc_bytes, ZKWG_MAIN_FP_MUL, ZKWG_MAIN_REVEAL_SUBSTRING, ZKWG_MAIN_COUNT_SUBSTRING. */
 #define ZKWG_ABI_VERSION 3
 
 /* `component main = ...` choices (the reference's own test mains). */
@@ -66,8 +66,17 @@ enum zkwg_main_kind {
   ZKWG_MAIN_EMAIL_VERIFIER = 0, /* EmailVerifier(maxHeader,maxBody,n,k,ignoreBodyHashCheck,0,0,0), public [pubkey] */
   ZKWG_MAIN_SHA256_BYTES = 1,   /* Sha256Bytes(maxHeader), public [paddedIn, paddedInLength] (sha-test.circom) */
   ZKWG_MAIN_RSA_VERIFIER = 2,   /* RSAVerifier65537(n,k), public [modulus] (rsa-test.circom) */
-  ZKWG_MAIN_FP_MUL = 3          /* FpMul(n,k), n*k <= 62, 2 <= k <= 17: inputs a, b, p in the pubkey / signature / message slots of the
+  ZKWG_MAIN_FP_MUL = 3,         /* FpMul(n,k), n*k <= 62, 2 <= k <= 17: inputs a, b, p in the pubkey / signature / message slots of the
                                    record (fp-mul-test.circom: FpMul(2,4); tests/fp-mul.test.ts:34-46) */
+  ZKWG_MAIN_REVEAL_SUBSTRING = 4, /* RevealSubstring(maxLength, maxSubstringLength, shouldCheckUniqueness), no public inputs
+                                   (helpers/reveal-substring.circom:13-50, reveal-substring-test.circom:5: (256, 16, 1)).
+                                   max_header = maxLength, max_body = maxSubstringLength, n = shouldCheckUniqueness (0 / 1), k = 0, every
+                                   flag 0; 2 <= max_body < max_header <= 65536, neither needs to be a multiple of 64 (the record pads).
+                                   in[] in ZKWG_IN_HEADER, substringStartIndex in ZKWG_IN_BODY_HASH_INDEX, substringLength in ZKWG_IN_BODY_LEN */
+  ZKWG_MAIN_COUNT_SUBSTRING = 5 /* CountSubstringOccurrences(maxLen, maxSubstringLen) (utils/array.circom:226-254,
+                                   count-substring-occurrences-test.circom:5: (1024, 128)).  max_header = maxLen, max_body =
+                                   maxSubstringLen, n = k = 0; 2 <= max_body <= max_header <= 65536.  in[] in ZKWG_IN_HEADER, substring[] in
+                                   ZKWG_IN_BODY.  Both mains: elements are bytes; no `.sym` layout, no Montgomery-form output (BAD_CONFIG) */
 };
 
 /* Witness layouts.  KEPT_V1 is the compact layout documented in DESIGN.md; SYM is KEPT_V1 re-ordered
@@ -76,9 +85,9 @@ enum zkwg_layout { ZKWG_LAYOUT_KEPT_V1 = 0, ZKWG_LAYOUT_SYM = 1 };
 
 typedef struct zkwg_config {
   uint32_t main_kind;                /* enum zkwg_main_kind */
-  uint32_t max_header;               /* maxHeadersLength (multiple of 64) */
-  uint32_t max_body;                 /* maxBodyLength   (multiple of 64; 0 if unused) */
-  uint32_t n;                        /* bits per RSA limb   (121) */
+  uint32_t max_header;               /* maxHeadersLength (multiple of 64); substring mains: maxLength / maxLen, any value up to 65536 */
+  uint32_t max_body;                 /* maxBodyLength   (multiple of 64; 0 if unused); substring mains: maxSubstringLength / maxSubstringLen */
+  uint32_t n;                        /* bits per RSA limb   (121); ZKWG_MAIN_REVEAL_SUBSTRING: shouldCheckUniqueness (0 / 1) */
   uint32_t k;                        /* number of RSA limbs (17)  */
   uint32_t ignore_body_hash_check;   /* template flag, email-verifier.circom:42 */
   uint32_t enable_header_masking;    /* template flag: headerMask input, maskedHeader output */
@@ -89,15 +98,15 @@ typedef struct zkwg_config {
 
 /* Fields of one packed input record (one record per email). */
 enum zkwg_input_field {
-  ZKWG_IN_HEADER = 0,         /* u8[max_header]  emailHeader / paddedIn            */
-  ZKWG_IN_BODY = 1,           /* u8[max_body]    emailBody                         */
+  ZKWG_IN_HEADER = 0,         /* u8[max_header]  emailHeader / paddedIn / in (substring mains) */
+  ZKWG_IN_BODY = 1,           /* u8[max_body]    emailBody / substring (ZKWG_MAIN_COUNT_SUBSTRING) */
   ZKWG_IN_PRECOMPUTED_SHA = 2,/* u8[32]          precomputedSHA                    */
   ZKWG_IN_PUBKEY = 3,         /* 17 x 16-byte LE limbs: pubkey / modulus           */
   ZKWG_IN_SIGNATURE = 4,      /* 17 x 16-byte LE limbs                             */
   ZKWG_IN_MESSAGE = 5,        /* 17 x 16-byte LE limbs (RSA main only)             */
   ZKWG_IN_HEADER_LEN = 6,     /* u32 emailHeaderLength / paddedInLength            */
-  ZKWG_IN_BODY_LEN = 7,       /* u32 emailBodyLength                               */
-  ZKWG_IN_BODY_HASH_INDEX = 8,/* u32 bodyHashIndex                                 */
+  ZKWG_IN_BODY_LEN = 7,       /* u32 emailBodyLength / substringLength (ZKWG_MAIN_REVEAL_SUBSTRING) */
+  ZKWG_IN_BODY_HASH_INDEX = 8,/* u32 bodyHashIndex / substringStartIndex (ZKWG_MAIN_REVEAL_SUBSTRING) */
   ZKWG_IN_HEADER_MASK = 9,    /* u8[max_header]  headerMask (enable_header_masking)  */
   ZKWG_IN_BODY_MASK = 10,     /* u8[max_body]    bodyMask   (enable_body_masking)    */
   ZKWG_IN_DECODED_BODY = 11,  /* u8[max_body]    decodedEmailBodyIn (remove_soft_line_breaks) */

@@ -313,6 +313,7 @@ static int create_impl(const zkwg_config* cfg_in, int device, const char* sym_te
     D.m_net = c->s.m_net; D.m_net_pw = c->s.m_net_pw; D.n_in = c->net.n_in;
   }
   if (getenv("ZKWG_DEBUG_SKIP_INV") && atoi(getenv("ZKWG_DEBUG_SKIP_INV")) && c->s.rsa.present) c->s.rsa.present = 2;  // profiling only
+  if (c->s.sub.present && (sym_text || r1cs)) { g_last_error = "the substring mains have no .sym / numbered layout"; delete c; return ZKWG_RC_BAD_CONFIG; }
   if (sym_text) {
     ZkSymLayout L;
     L.allow_holes = r1cs != nullptr;
@@ -988,6 +989,11 @@ int zkwg_prepare_device(zkwg_circuit_t* c, const void* d_in, uint64_t n, void* d
     hipLaunchKernelGGL(zk_rsa, dim3(ne), dim3(64), dyn, st, s, B);
   }
   if (s.fpg.present && (pm & 16u)) hipLaunchKernelGGL(zk_fpmul_small, dim3((ne + 63) / 64), dim3(64), 0, st, s, B);   // (timed in zk_rsa's slot)
+  if (s.sub.present && (pm & 16u)) {   // substring mains: one wavefront per email, in[] and the substring in LDS (timed in zk_rsa's slot)
+    const u32 lds = zk_sub_lds_bytes(s.sub.L, s.sub.S);
+    if (lds > 48u * 1024u) hipFuncSetAttribute((const void*)zk_substr, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+    hipLaunchKernelGGL(zk_substr, dim3(ne), dim3(64), lds, st, s, B);
+  }
   if (tm) hipEventRecord(evs[++ki], st);
   if (pos9) {
     // one lane per email once the batch supplies >= 16 wavefronts of them; one wavefront per email below
@@ -1048,6 +1054,7 @@ static int expand_impl(zkwg_circuit_t* c, const void* d_in, uint64_t n, const vo
   if (count == 0) return ZKWG_RC_OK;
   const ZkSched& s = c->s;
   if (abc && !c->abc_m) return ZKWG_RC_BAD_CONFIG;
+  if (mont && s.sub.present) return ZKWG_RC_BAD_CONFIG;   // substring mains: no Montgomery-form output
   // the descriptor table written from: the attached system's A.w | B.w | C.w, a numbered circuit's wires, or none (kept-v1 pieces)
   const ZkO0Dev* OD = abc ? &c->abcd : (c->full_W ? &c->o0d : nullptr);
   if (first + count > n || out_stride < (abc ? 3 * c->abc_m : out_W(c)) * 32 || (out_stride & 15)) return ZKWG_RC_BAD_ARG;
@@ -1115,7 +1122,8 @@ static int expand_impl(zkwg_circuit_t* c, const void* d_in, uint64_t n, const vo
       if (units3 > 0x7fffffffull) return ZKWG_RC_BAD_ARG;
       if (mont) hipLaunchKernelGGL(zk_image_to_mont, dim3((u32)((conv + 255) / 256)), dim3(256), 0, st, A);
       const dim3 g3((u32)units3), b3(256);
-      hipLaunchKernelGGL(mont ? zk_expand3_mont : zk_expand3, g3, b3, 0, st, A);
+      if (s.sub.present) hipLaunchKernelGGL(zk_expand3_subm, g3, b3, 0, st, A);   // (mont was refused above)
+      else hipLaunchKernelGGL(mont ? zk_expand3_mont : zk_expand3, g3, b3, 0, st, A);
     }
   }
   if (tm) { hipEventRecord(evs[1], st); c->ev_valid = true; c->launches++; }
@@ -1144,6 +1152,7 @@ int zkwg_circuit_attach_r1cs(zkwg_circuit_t* c, const uint8_t* r1cs, uint64_t le
   std::lock_guard<std::mutex> hb_lock(c->hb_mutex);
   std::lock_guard<std::mutex> lock(c->dev_mutex);
   if (c->abc_m) { g_last_error = "attach_r1cs: the handle already has a constraint system"; return ZKWG_RC_BAD_CONFIG; }
+  if (c->s.sub.present) { g_last_error = "attach_r1cs: not available for the substring mains"; return ZKWG_RC_BAD_CONFIG; }
   try {
     ZkR1csHost R;
     if (!zk_r1cs_parse(r1cs, len, R)) { g_last_error = "the .r1cs file could not be parsed: " + R.err; return ZKWG_RC_BAD_CONFIG; }
@@ -1448,7 +1457,7 @@ int zkwg_expand_host(const zkwg_circuit_t* c, const uint8_t* records, uint64_t n
         u8* dst = w + 32 * a;
         switch (sg.type) {
 #define ZK_X(T, D) case T: zk_host_segment<D>(sg, cx, R, r0, cnt, dst); break;
-          ZK_FOR_SEG_TYPES(ZK_X)
+          ZK_FOR_SEG_TYPES_ALL(ZK_X)
 #undef ZK_X
           default: memset(dst, 0, 32ull * cnt); break;
         }
@@ -1774,6 +1783,8 @@ uint64_t zkwg_write_sym(const zkwg_circuit_t* c, char* out, uint64_t cap) {
     case ZKWG_MAIN_SHA256_BYTES: zk_walk_main_sha(w, tmp); break;
     case ZKWG_MAIN_RSA_VERIFIER: zk_walk_main_rsa(w, tmp); break;
     case ZKWG_MAIN_FP_MUL: zk_walk_main_fpmul(w, tmp, tmp.fpg.n, tmp.fpg.k); break;
+    case ZKWG_MAIN_REVEAL_SUBSTRING: zk_walk_main_reveal(w, tmp, tmp.sub.L, tmp.sub.S, tmp.sub.uniq); break;
+    case ZKWG_MAIN_COUNT_SUBSTRING: zk_walk_main_count(w, tmp, tmp.sub.L, tmp.sub.S); break;
     case ZKWG_MAIN_EMAIL_VERIFIER: zk_walk_main_ev(w, tmp); break;
   }
   return pos;

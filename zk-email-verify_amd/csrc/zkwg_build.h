@@ -48,13 +48,19 @@ static bool build_sched(const zkwg_config& cfg, ZkSched& s, std::vector<ZkSeg>& 
   if (cfg.remove_soft_line_breaks && (cfg.main_kind != ZKWG_MAIN_EMAIL_VERIFIER || cfg.ignore_body_hash_check)) return false;
   if ((cfg.enable_header_masking || cfg.enable_body_masking) && cfg.main_kind != ZKWG_MAIN_EMAIL_VERIFIER) return false;
   if (cfg.enable_body_masking && cfg.ignore_body_hash_check) return false;
-  if (cfg.max_header % 64 != 0 || cfg.max_body % 64 != 0) return false;
+  // the substring mains take any lengths: their record slots are padded to the alignment the other mains require of the parameters
+  const bool substr = cfg.main_kind == ZKWG_MAIN_REVEAL_SUBSTRING || cfg.main_kind == ZKWG_MAIN_COUNT_SUBSTRING;
+  if (substr) {
+    if (cfg.max_header > 65536 || cfg.max_body < 2 || cfg.max_body > cfg.max_header || cfg.k || cfg.ignore_body_hash_check ||
+        cfg.remove_soft_line_breaks || net) return false;
+    if (cfg.main_kind == ZKWG_MAIN_REVEAL_SUBSTRING ? (cfg.max_body == cfg.max_header || cfg.n > 1) : cfg.n != 0) return false;
+  } else if (cfg.max_header % 64 != 0 || cfg.max_body % 64 != 0) return false;
   s.main_kind = cfg.main_kind;
   s.n = cfg.n; s.k = cfg.k; s.ignore_body = cfg.ignore_body_hash_check;
   // input record
   u32 off = 0;
-  s.in_off[ZKWG_IN_HEADER] = off; off += cfg.max_header;
-  s.in_off[ZKWG_IN_BODY] = off; off += cfg.max_body;
+  s.in_off[ZKWG_IN_HEADER] = off; off += (cfg.max_header + 63u) & ~63u;
+  s.in_off[ZKWG_IN_BODY] = off; off += (cfg.max_body + 63u) & ~63u;
   s.in_off[ZKWG_IN_PRECOMPUTED_SHA] = off; off += 32;
   off = (off + 15u) & ~15u;
   s.in_off[ZKWG_IN_PUBKEY] = off; off += 17 * 16;
@@ -129,6 +135,17 @@ static bool build_sched(const zkwg_config& cfg, ZkSched& s, std::vector<ZkSeg>& 
       s.nframes = 0;
       zk_walk_main_fpmul(w, s, cfg.n, cfg.k);
       break;
+    case ZKWG_MAIN_REVEAL_SUBSTRING:
+      s.nframes = 0;
+      zk_walk_main_reveal(w, s, cfg.max_header, cfg.max_body, cfg.n);
+      // IsZero(difference[j]): |(in - substring) substring| reaches 255 * 255 (utils/array.circom:211-212)
+      if (cfg.n) max_small = 255 * 255;
+      break;
+    case ZKWG_MAIN_COUNT_SUBSTRING:
+      s.nframes = 0;
+      zk_walk_main_count(w, s, cfg.max_header, cfg.max_body);
+      max_small = 255 * 255;
+      break;
     default:
       return false;
   }
@@ -197,6 +214,8 @@ static inline void zk_collect_names(ZkSched tmp, std::vector<std::string>& names
   switch (tmp.main_kind) {
     case ZKWG_MAIN_SHA256_BYTES: zk_walk_main_sha(w, tmp); break;
     case ZKWG_MAIN_RSA_VERIFIER: zk_walk_main_rsa(w, tmp); break;
+    case ZKWG_MAIN_REVEAL_SUBSTRING: zk_walk_main_reveal(w, tmp, tmp.sub.L, tmp.sub.S, tmp.sub.uniq); break;
+    case ZKWG_MAIN_COUNT_SUBSTRING: zk_walk_main_count(w, tmp, tmp.sub.L, tmp.sub.S); break;
     default: zk_walk_main_ev(w, tmp); break;
   }
 }

@@ -301,6 +301,31 @@ struct ZkDecNetQ {
   }
 };
 
+// CountSubstringOccurrences(L, S) match matrix (utils/array.circom:196-254; zkwg_layout.h zk_walk_count_substring): slot r is element q of
+// the 4 S + 2 kept signals of matches[i], i = i0 + r / (4 S + 2).  zk_substr left the substring and, per start position i, the number
+// mlen[i] of leading positions whose difference is zero; everything else derives from one record byte and one substring word.
+struct ZkDecSubm {
+  const u8* __restrict__ in; const u32* __restrict__ sub; const u32* __restrict__ mlen; u32 S, L, i0, per, magic; int half;
+  ZK_DEC ZkDecSubm(const ZkSeg& sg, const ZkCtx& cx)
+      : in(cx.rec + sg.src), sub(cx.small + sg.b), mlen(cx.small + sg.b + sg.a), S(sg.a), L((sg.c & 0xffffu) + 1u), i0(sg.c >> 16),
+        per(4u * sg.a + 2u), magic(sg.pad), half(cx.half) {}
+  ZK_DEC u32 operator()(u32 r) const {
+    const u32 t = zk_udiv(r, per, magic), q = r - t * per, i = i0 + t;
+    if (q < S) return (u32)(q < mlen[i]);                       // matchAccumulator[q + 1]
+    u32 j, kind;                                                // kind 0: difference[j], 1: isz.out, 2: isz.inv
+    if (q < 2u * S) { j = q - S; kind = 0u; }
+    else {
+      const u32 u = q - 2u * S;
+      if (u < 2u) { const int s0 = (int)sub[0]; return u ? zk_inv_code(s0, half) : (u32)(s0 == 0); }   // IsZero()(substring[0])
+      j = (u - 2u) >> 1; kind = 1u + (u & 1u);
+    }
+    const int s = (int)sub[j], x = i + j < L ? (int)in[i + j] : 0;   // in[i + j], 0 past the end (:238-242)
+    const int d = (x - s) * s;
+    if (kind == 0u) return d >= 0 ? (u32)d : (ZK_REF_MINUS | (u32)(-d));
+    return kind == 2u ? zk_inv_code(d, half) : (u32)(d == 0);
+  }
+};
+
 // every segment type with its decoder: ZK_FOR_SEG_TYPES(X) expands X(type, Decoder) once per type
 #define ZK_FOR_SEG_TYPES(X)                                                                                           \
   X(ZSEG_SMALL, ZkDecSmall) X(ZSEG_FR, ZkDecFr) X(ZSEG_BITS, ZkDecBits)                                                \
@@ -310,10 +335,15 @@ struct ZkDecNetQ {
   X(ZSEG_REGSEL, ZkDecRegSel) X(ZSEG_VSHIFT, ZkDecVShift) X(ZSEG_B64BITS, ZkDecB64<false>) X(ZSEG_B64, ZkDecB64<true>) \
   X(ZSEG_DFA, ZkDecDfa) X(ZSEG_RSLB, ZkDecRslb) X(ZSEG_NETP, ZkDecNetP) X(ZSEG_NETQ, ZkDecNetQ)
 #define ZK_COMMA ,
+// ZSEG_SUBM stays out of the common switch: zk_expand3's register budget (64 VGPRs, 8 wavefronts per SIMD) and rate are held as they
+// are; the substring mains expand through their own instantiation (SUBM = true: zk_expand3_subm, the host expansion)
+#define ZK_FOR_SEG_TYPES_ALL(X) ZK_FOR_SEG_TYPES(X) X(ZSEG_SUBM, ZkDecSubm)
 
 // one slot of any segment (pieces that straddle segments, the numbered-circuit expansion and the linear-row kernels
 // reach slots one by one)
+template <bool SUBM = false>
 ZK_DEC inline u32 zk_decode_any(const ZkSeg& sg, u32 r, const ZkCtx& cx) {
+  if constexpr (SUBM) { if (sg.type == ZSEG_SUBM) return ZkDecSubm(sg, cx)(r); }
   switch (sg.type) {
 #define ZK_X(T, D) case T: return D(sg, cx)(r);
     ZK_FOR_SEG_TYPES(ZK_X)
@@ -323,8 +353,16 @@ ZK_DEC inline u32 zk_decode_any(const ZkSeg& sg, u32 r, const ZkCtx& cx) {
 }
 // K slots r0 + i0, r0 + i0 + 64, ... of ONE segment (slots at or beyond `n` give 0): the type switch is taken once and the
 // K decodes are straight-line code, so their image reads are in flight together
-template <int K>
+template <int K, bool SUBM = false>
 __device__ __forceinline__ void zk_decode_k(const ZkSeg& sg, u32 r0, u32 i0, u32 n, const ZkCtx& cx, u32 (&code)[K]) {
+  if constexpr (SUBM) {
+    if (sg.type == ZSEG_SUBM) {
+      const ZkDecSubm dec(sg, cx);
+#pragma unroll
+      for (int k = 0; k < K; ++k) { const u32 i = i0 + 64u * (u32)k; code[k] = i < n ? dec(r0 + i) : 0u; }
+      return;
+    }
+  }
   switch (sg.type) {
 #define ZK_X(T, D) case T: { const D dec(sg, cx); _Pragma("unroll") for (int k = 0; k < K; ++k) { const u32 i = i0 + 64u * (u32)k; code[k] = i < n ? dec(r0 + i) : 0u; } break; }
     ZK_FOR_SEG_TYPES(ZK_X)

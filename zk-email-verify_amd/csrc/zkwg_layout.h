@@ -289,6 +289,91 @@ static inline void zk_walk_main_fpmul(ZkWalker& w, ZkSched& s, u32 n, u32 k) {
   s.n_public = 0;
 }
 
+// ------------------------------------------------------------------ substring helpers (helpers/reveal-substring.circom, utils/array.circom)
+// SelectSubArray(L, S) (utils/array.circom:78-101): out[S], shifter = VarShiftLeft(L, S) (tmp[log2Ceil(L)][L], n2b.out),
+// gts[S] = GreaterThan(log2Ceil(S)) (lt.n2b.out).  `m_shift` is the small word holding startIndex.
+static inline void zk_alloc_select_sub_array(ZkWalker& w, ZkSubLayout& U) {
+  U.m_in = w.alloc_small(U.L);
+  U.b_shift = w.alloc_bits(1);
+  U.b_gts = w.alloc_bits(U.S);
+}
+static inline void zk_walk_select_sub_array(ZkWalker& w, const std::string& p, const ZkSubLayout& U, u32 m_shift) {
+  const u32 bl = zk_log2ceil(U.L), lg = zk_log2ceil(U.S);
+  w.seg(ZSEG_SMALL, U.S, U.m_sub);
+  w.arr(p + ".out", U.S);
+  w.seg(ZSEG_VSHIFT, (u64)bl * U.L, m_shift, U.L, U.m_in);
+  w.arr(p + ".shifter.tmp", bl * U.L);
+  w.seg(ZSEG_BITS, bl, U.b_shift, bl, 1);
+  w.arr(p + ".shifter.n2b.out", bl);
+  w.seg(ZSEG_BITS, (u64)U.S * (lg + 1), U.b_gts, lg + 1, 1);
+  for (u32 i = 0; i < U.S; ++i) w.arr(zk_idx(p + ".gts", i) + ".lt.n2b.out", lg + 1);
+}
+// CountSubstringOccurrences(L, S) (utils/array.circom:226-254): matches[L] = CheckSubstringMatch(S) (:196-217), 4 S + 2 kept
+// signals each; `count`, summer.sums, isMatch, isZeroDifference, firstElementNonZero and matchAccumulator[0] are linear.
+// A segment holds fewer than 2^30 slots: whole components per segment, the first one's index travels in c.
+static inline void zk_walk_count_substring(ZkWalker& w, const std::string& p, const ZkSubLayout& U) {
+  const u64 per = 4ull * U.S + 2;
+  const u32 step = (u32)std::max<u64>(1, 0x40000000ull / per);
+  for (u32 i0 = 0; i0 < U.L; i0 += step) {
+    const u32 n = std::min(step, U.L - i0);
+    w.seg(ZSEG_SUBM, n * per, U.in_in, U.S, U.m_sub, (U.L - 1u) | (i0 << 16));
+  }
+  if (!w.names) { w.skip(per * U.L); return; }
+  for (u32 i = 0; i < U.L; ++i) {
+    const std::string q = zk_idx(p + ".matches", i);
+    for (u32 j = 1; j <= U.S; ++j) w.one(zk_idx(q + ".matchAccumulator", j));
+    w.arr(q + ".difference", U.S);
+    w.one(q + ".anon_IsZero.out"); w.one(q + ".anon_IsZero.inv");
+    for (u32 j = 0; j < U.S; ++j) { w.one(zk_idx(q + ".anon_IsZero", j) + ".out"); w.one(zk_idx(q + ".anon_IsZero", j) + ".inv"); }
+  }
+}
+static inline void zk_sub_record(ZkSubLayout& U, const ZkSched& s, u32 kind, u32 L, u32 S, u32 uniq) {
+  U.present = kind; U.L = L; U.S = S; U.uniq = uniq;
+  U.in_in = s.in_off[0]; U.in_sub = s.in_off[1]; U.in_len = s.in_off[7]; U.in_start = s.in_off[8];
+}
+// main = RevealSubstring(L, S, uniq), no public inputs (tests/test-circuits/reveal-substring-test.circom:5;
+// helpers/reveal-substring.circom:13-50).  The three anonymous LessThan call sites (:23, :27, :32) are named
+// anon_LessThan_start / _length / _sum.
+static inline void zk_walk_main_reveal(ZkWalker& w, ZkSched& s, u32 L, u32 S, u32 uniq) {
+  ZkSubLayout& U = s.sub;
+  zk_sub_record(U, s, 1, L, S, uniq);
+  s.m_one = w.alloc_small(1);
+  U.m_sub = w.alloc_small(S);                   // (m_one and m_sub are consecutive)
+  if (uniq) w.alloc_small(L);                   // the leading-match lengths follow the substring (ZSEG_SUBM)
+  U.m_start = w.alloc_small(2);
+  U.b_lt = w.alloc_bits(3);
+  zk_alloc_select_sub_array(w, U);
+  w.seg(ZSEG_SMALL, 1 + S, s.m_one);
+  w.one("one");
+  w.arr("main.substring", S);
+  w.seg(ZSEG_IN8, L, U.in_in); w.arr("main.in", L);
+  w.seg(ZSEG_SMALL, 2, U.m_start);
+  w.one("main.substringStartIndex"); w.one("main.substringLength");
+  const u32 b0 = zk_log2ceil(L) + 1, b1 = zk_log2ceil((u64)S + 1) + 1, b2 = zk_log2ceil((u64)L + 1) + 1;
+  w.seg(ZSEG_BITS, b0, U.b_lt, b0, 1); w.arr("main.anon_LessThan_start.n2b.out", b0);
+  w.seg(ZSEG_BITS, b1, U.b_lt + 1, b1, 1); w.arr("main.anon_LessThan_length.n2b.out", b1);
+  w.seg(ZSEG_BITS, b2, U.b_lt + 2, b2, 1); w.arr("main.anon_LessThan_sum.n2b.out", b2);
+  zk_walk_select_sub_array(w, "main.selectSubArray", U, U.m_start);
+  if (uniq) zk_walk_count_substring(w, "main.countSubstringOccurrences", U);
+  s.n_public = S;   // outputs only
+}
+// main = CountSubstringOccurrences(L, S), no public inputs (tests/test-circuits/count-substring-occurrences-test.circom:5)
+static inline void zk_walk_main_count(ZkWalker& w, ZkSched& s, u32 L, u32 S) {
+  ZkSubLayout& U = s.sub;
+  zk_sub_record(U, s, 2, L, S, 1);
+  s.m_one = w.alloc_small(1);
+  U.m_count = w.alloc_small(1);                 // (m_one and m_count are consecutive)
+  U.m_sub = w.alloc_small(S);
+  w.alloc_small(L);
+  w.seg(ZSEG_SMALL, 2, s.m_one);
+  w.one("one");
+  w.one("main.count");
+  w.seg(ZSEG_IN8, L, U.in_in); w.arr("main.in", L);
+  w.seg(ZSEG_IN8, S, U.in_sub); w.arr("main.substring", S);
+  zk_walk_count_substring(w, "main", U);
+  s.n_public = 1;
+}
+
 // ------------------------------------------------------------------ BodyHashRegex DFA circuit (zkwg v1)
 // [EXT] zk-regex's generated body_hash_regex.circom is absent; this is zkwg's own circuit of the same
 // style over the DFA tables of tools/gen_bh_dfa.py (restated literally in oracle/pyref/zkemail.py

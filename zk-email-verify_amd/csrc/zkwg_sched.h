@@ -56,7 +56,11 @@ enum ZkSegType : u32 {
                     // src + r % a at position b + r / a (+ the descriptor's own offset) (zkwg_net_core.h ZkNetDec)
   ZSEG_NETQ = 22,   // a long run of the same region with a DENSE table: src = the table's offset in the region's tables, a = period, b = position of
                     // period 0; slot r = table[(fstate, byte of position b + r / a)][r % a] -- no descriptor (zkwg_net_core.h zk_netq_word)
-  ZSEG_NTYPES = 23
+  ZSEG_SUBM = 23,   // CountSubstringOccurrences match matrix (utils/array.circom:196-254): a = maxSubstringLen S, c = maxLen; per component i a period of
+                    // 4 S + 2 slots: matchAccumulator[1..S], difference[S], IsZero(substring[0]) (out, inv), S x IsZero(difference[j]) (out, inv);
+                    // in[] = record bytes at src, substring = small[b .. b + S), leading-match lengths = small[b + S .. b + S + c)
+                    // (decoded by ZkDecSubm, which only zk_expand3_subm and the host expansion instantiate: zkwg_kernels_substr.hip)
+  ZSEG_NTYPES = 24
 };
 
 // ZSEG_RSLB kinds (helpers/remove-soft-line-breaks.circom:14-126); enc = the emailBody bytes at src
@@ -110,6 +114,7 @@ ZK_HD u32 zk_seg_period(const ZkSeg& g) {
     case ZSEG_REGSEL: return g.a + 7u;
     case ZSEG_VSHIFT: return g.a;
     case ZSEG_NETP: case ZSEG_NETQ: return g.a;
+    case ZSEG_SUBM: return 4u * g.a + 2u;
     default: return 0;
   }
 }
@@ -174,6 +179,23 @@ struct ZkFpgLayout {
   u32 f_carry;           // fr: tCheck.carry[2k-1]
   u32 b_carry;           // bits: tCheck.carryRangeChecks[2k-2] (one word each)
 };
+// main = RevealSubstring(L, S, uniq) / CountSubstringOccurrences(L, S) (helpers/reveal-substring.circom:13-50,
+// utils/array.circom:226-254; zkwg_substr_core.h)
+struct ZkSubLayout {
+  u32 present;           // 0: absent, 1: RevealSubstring, 2: CountSubstringOccurrences alone
+  u32 L, S, uniq;        // maxLength, maxSubstringLength, 1: the count part is in the layout
+  u32 in_in, in_sub;     // record offsets of in[L] and (count main) substring[S]
+  u32 in_start, in_len;  // record offsets of substringStartIndex, substringLength (u32)
+  u32 m_sub;             // small: the substring searched for / revealed [S], then (uniq) the leading-match length of every start position [L]
+  u32 m_start;           // small: substringStartIndex, substringLength
+  u32 m_in;              // small: in[L] as words (VarShiftLeft.tmp reads them)
+  u32 m_count;           // small: count (count main: the output, follows m_one)
+  u32 b_lt;              // bits: 3 words, the Num2Bits inputs of the three LessThan range checks
+  u32 b_shift;           // bits: 1 word, substringStartIndex (VarShiftLeft.n2b)
+  u32 b_gts;             // bits: S words, the Num2Bits inputs of gts[i] = GreaterThan(log2Ceil(S))(length, i)
+};
+// bytes of zk_substr's working set (LDS): in[] | substring[] | 64 partial counts + the failure flag
+ZK_HD u32 zk_sub_lds_bytes(u32 L, u32 S) { return ((L + 15u) & ~15u) + ((S + 15u) & ~15u) + 65u * 4u; }
 // RSAVerifier65537(121,17) (lib/rsa.circom:13-46)
 struct ZkRsaLayout {
   u32 present;                 // 0 = circuit has no RSA block
@@ -212,6 +234,7 @@ struct ZkSched {
   u32 m_hdr_len;         // small: emailHeaderLength / paddedInLength
   ZkRsaLayout rsa;
   ZkFpgLayout fpg;       // main = FpMul(n, k) with small parameters
+  ZkSubLayout sub;       // main = RevealSubstring / CountSubstringOccurrences
   // EmailVerifier main (email-verifier.circom:42-174)
   u32 f_out;             // fr: pubkeyHash, shaHi, shaLo
   u32 f_pos;             // fr: 420 Poseidon S-box signals

@@ -18,6 +18,8 @@ const addon = require(path.join(__dirname, 'zkwg_addon.node'));
 const FIELD_MODULUS = 21888242871839275222246405745257275088548364400416034343698204186575808495617n;
 const BASE_FIELD_MODULUS = 21888242871839275222246405745257275088696311157297823662689037894645226208583n;   // BN254 Fq (a .zkey states both primes)
 const MAIN_EMAIL_VERIFIER = 0, MAIN_SHA256_BYTES = 1, MAIN_RSA_VERIFIER = 2, MAIN_FP_MUL = 3;
+// RevealSubstring(maxHeader, maxBody, n) / CountSubstringOccurrences(maxHeader, maxBody): helpers/reveal-substring.circom, utils/array.circom:226-254
+const MAIN_REVEAL_SUBSTRING = 4, MAIN_COUNT_SUBSTRING = 5;
 const IN = { HEADER: 0, BODY: 1, PRECOMPUTED_SHA: 2, PUBKEY: 3, SIGNATURE: 4, MESSAGE: 5, HEADER_LEN: 6, BODY_LEN: 7, BODY_HASH_INDEX: 8, HEADER_MASK: 9, BODY_MASK: 10, DECODED_BODY: 11, RANGE_FLAGS: 12 };
 
 function norm(v) {
@@ -65,6 +67,8 @@ class Circuit {
     if (o.mainKind === MAIN_SHA256_BYTES) return { paddedIn: o.maxHeader, paddedInLength: 1 };
     if (o.mainKind === MAIN_RSA_VERIFIER) return { message: o.k, signature: o.k, modulus: o.k };
     if (o.mainKind === MAIN_FP_MUL) return { a: o.k, b: o.k, p: o.k };   // FpMul(n, k) (tests/test-circuits/fp-mul-test.circom)
+    if (o.mainKind === MAIN_REVEAL_SUBSTRING) return { in: o.maxHeader, substringStartIndex: 1, substringLength: 1 };
+    if (o.mainKind === MAIN_COUNT_SUBSTRING) return { in: o.maxHeader, substring: o.maxBody };
     const s = { emailHeader: o.maxHeader, emailHeaderLength: 1, pubkey: o.k, signature: o.k };
     if (o.enableHeaderMasking) s.headerMask = o.maxHeader;
     if (!o.ignoreBodyHashCheck) {
@@ -125,6 +129,14 @@ class Circuit {
     } else if (o.mainKind === MAIN_FP_MUL) {
       // the chunks of a, b, p travel in the pubkey / signature / message slots of the record (include/zkwg.h)
       limbs(IN.PUBKEY, flat.a, 'a'); limbs(IN.SIGNATURE, flat.b, 'b'); limbs(IN.MESSAGE, flat.p, 'p');
+    } else if (o.mainKind === MAIN_REVEAL_SUBSTRING || o.mainKind === MAIN_COUNT_SUBSTRING) {
+      // in[] / substring[] are bytes (include/zkwg.h): anything else is refused here, not failed as an assertion
+      for (const key of ['in', 'substring']) {
+        if (flat[key] && flat[key].some((v) => v > 255n)) throw new Error('input signal ' + key + ' holds a value that is not a byte');
+      }
+      bytes(IN.HEADER, flat.in, 'in');
+      if (o.mainKind === MAIN_COUNT_SUBSTRING) bytes(IN.BODY, flat.substring, 'substring');
+      else { u32(IN.BODY_HASH_INDEX, flat.substringStartIndex[0], 'substringStartIndex'); u32(IN.BODY_LEN, flat.substringLength[0], 'substringLength'); }
     } else {
       bytes(IN.HEADER, flat.emailHeader, 'emailHeader'); u32(IN.HEADER_LEN, flat.emailHeaderLength[0], 'emailHeaderLength');
       limbs(IN.PUBKEY, flat.pubkey, 'pubkey'); limbs(IN.SIGNATURE, flat.signature, 'signature');
@@ -407,4 +419,5 @@ function symbols(circuit) {
   return names;
 }
 
-module.exports = { symbols, R1cs, Circuit, WitnessCalculator, MultiCalculator, Prover, Tester, tester, wtns, groth16, FIELD_MODULUS, MAIN_EMAIL_VERIFIER, MAIN_SHA256_BYTES, MAIN_RSA_VERIFIER, MAIN_FP_MUL };
+module.exports = { symbols, R1cs, Circuit, WitnessCalculator, MultiCalculator, Prover, Tester, tester, wtns, groth16, FIELD_MODULUS, MAIN_EMAIL_VERIFIER, MAIN_SHA256_BYTES, MAIN_RSA_VERIFIER, MAIN_FP_MUL,
+  MAIN_REVEAL_SUBSTRING, MAIN_COUNT_SUBSTRING };

@@ -14,7 +14,8 @@ is no CPU fallback (a missing library or GPU raises).
 import ctypes as C
 
 from . import _lib
-from ._lib import Config, MAIN_EMAIL_VERIFIER, MAIN_SHA256_BYTES, MAIN_RSA_VERIFIER, MAIN_FP_MUL
+from ._lib import (Config, MAIN_EMAIL_VERIFIER, MAIN_SHA256_BYTES, MAIN_RSA_VERIFIER, MAIN_FP_MUL, MAIN_REVEAL_SUBSTRING,
+                   MAIN_COUNT_SUBSTRING)
 
 FIELD_MODULUS = 21888242871839275222246405745257275088548364400416034343698204186575808495617
 
@@ -47,7 +48,9 @@ def _limbs_bytes(vals, n_limbs=17):
 # CircuitInput signal name -> packed record field (include/zkwg.h enum zkwg_input_field)
 _FIELD_OF = {"emailHeader": 0, "paddedIn": 0, "emailBody": 1, "precomputedSHA": 2, "pubkey": 3, "modulus": 3, "a": 3,
              "signature": 4, "b": 4, "message": 5, "p": 5, "emailHeaderLength": 6, "paddedInLength": 6, "emailBodyLength": 7,
-             "bodyHashIndex": 8, "headerMask": 9, "bodyMask": 10, "decodedEmailBodyIn": 11}
+             "bodyHashIndex": 8, "headerMask": 9, "bodyMask": 10, "decodedEmailBodyIn": 11,
+             # RevealSubstring / CountSubstringOccurrences (helpers/reveal-substring.circom:16-18, utils/array.circom:229-230)
+             "in": 0, "substring": 1, "substringLength": 7, "substringStartIndex": 8}
 
 
 class Circuit:
@@ -126,6 +129,10 @@ class Circuit:
             return {"message": c.k, "signature": c.k, "modulus": c.k}
         if c.main_kind == MAIN_FP_MUL:
             return {"a": c.k, "b": c.k, "p": c.k}
+        if c.main_kind == MAIN_REVEAL_SUBSTRING:
+            return {"in": c.max_header, "substringStartIndex": 1, "substringLength": 1}
+        if c.main_kind == MAIN_COUNT_SUBSTRING:
+            return {"in": c.max_header, "substring": c.max_body}
         sizes = {"emailHeader": c.max_header, "emailHeaderLength": 1, "pubkey": c.k, "signature": c.k}
         if c.enable_header_masking:
             sizes["headerMask"] = c.max_header
@@ -191,6 +198,17 @@ class Circuit:
         elif c.main_kind == MAIN_FP_MUL:
             # the chunks of a, b, p travel in the pubkey / signature / message slots of the record
             pub = as_limbs(flat["a"], "a"); sig = as_limbs(flat["b"], "b"); msg = as_limbs(flat["p"], "p")
+        elif c.main_kind in (MAIN_REVEAL_SUBSTRING, MAIN_COUNT_SUBSTRING):
+            # the templates compare bytes: (in - substring) * substring has to stay inside the inverse table
+            for key in ("in", "substring"):
+                if key in flat and any(v > 255 for v in flat[key]):
+                    raise ZkwgError(f"input signal {key} holds a value that is not a byte")
+            header = bytes(flat["in"])
+            if c.main_kind == MAIN_COUNT_SUBSTRING:
+                body = bytes(flat["substring"])
+            else:
+                bhi = as_u32(flat["substringStartIndex"][0], "substringStartIndex")
+                blen = as_u32(flat["substringLength"][0], "substringLength")
         else:
             header = as_bytes(flat["emailHeader"], "emailHeader")
             hlen = as_u32(flat["emailHeaderLength"][0], "emailHeaderLength")
@@ -422,6 +440,11 @@ class Circuit:
         (bytearray of 32 W bytes whose produced slots are filled) in place."""
         arr = (C.c_uint8 * len(witness)).from_buffer(witness)
         _check(self.lib.zkwg_linear_complete_host(self.h, arr))
+
+    def calculate_witness(self, inp):
+        """`circuit.calculateWitness(input)` for one CircuitInput dict -> list of ints; "Assert Failed" when a constraint of the
+        circuit does not hold for the input (status 4)."""
+        return WitnessCalculator(self).calculateWitness(inp)
 
     def symbols(self):
         """[(slot, name)] of the layout (the .sym table)."""
@@ -726,6 +749,12 @@ class WitnessCalculator:
                 data = zr.write_r1cs(len(sym), zr.rsa_main_constraints(sym), 0, 17, 34)
             elif cfg.main_kind == MAIN_FP_MUL:
                 data = zr.write_r1cs(len(sym), zr.fp_mul_main_constraints(sym, cfg.n, cfg.k), cfg.k, 0, 3 * cfg.k)
+            elif cfg.main_kind == MAIN_REVEAL_SUBSTRING:
+                data = zr.write_r1cs(len(sym), zr.reveal_substring_main_constraints(sym, cfg.max_header, cfg.max_body, cfg.n),
+                                     cfg.max_body, 0, cfg.max_header + 2)
+            elif cfg.main_kind == MAIN_COUNT_SUBSTRING:
+                data = zr.write_r1cs(len(sym), zr.count_substring_main_constraints(sym, cfg.max_header, cfg.max_body),
+                                     1, 0, cfg.max_header + cfg.max_body)
             else:
                 data = zr.email_verifier_r1cs(sym, cfg.max_header, cfg.max_body, cfg.enable_header_masking,
                                               cfg.enable_body_masking, cfg.remove_soft_line_breaks, cfg.ignore_body_hash_check)

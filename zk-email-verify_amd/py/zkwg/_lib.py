@@ -66,6 +66,7 @@ class DkimVerifyArgs(C.Structure):   # zkwg_dkim_verify_args
 DKIM_SKIP_BODY_HASH = 1
 
 MAIN_EMAIL_VERIFIER, MAIN_SHA256_BYTES, MAIN_RSA_VERIFIER, MAIN_FP_MUL = 0, 1, 2, 3
+MAIN_REVEAL_SUBSTRING, MAIN_COUNT_SUBSTRING = 4, 5   # RevealSubstring(L, S, uniq), CountSubstringOccurrences(L, S): max_header = L, max_body = S, n = uniq
 (IN_HEADER, IN_BODY, IN_PRECOMPUTED_SHA, IN_PUBKEY, IN_SIGNATURE, IN_MESSAGE,
  IN_HEADER_LEN, IN_BODY_LEN, IN_BODY_HASH_INDEX, IN_HEADER_MASK, IN_BODY_MASK, IN_DECODED_BODY,
  IN_RANGE_FLAGS) = range(13)

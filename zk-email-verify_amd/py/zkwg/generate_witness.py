@@ -22,6 +22,12 @@ def circuit_kwargs(arg):
         return dict(main_kind=zkwg.MAIN_EMAIL_VERIFIER, max_header=p[0], max_body=p[1], n=p[2], k=p[3],
                     ignore_body_hash_check=p[4], enable_header_masking=p[5], enable_body_masking=p[6],
                     remove_soft_line_breaks=p[7])
+    m = re.fullmatch(r"\s*RevealSubstring\(\s*(\d+)\s*,\s*(\d+)\s*,\s*([01])\s*\)\s*", arg)
+    if m:   # helpers/reveal-substring.circom:13
+        return dict(main_kind=zkwg.MAIN_REVEAL_SUBSTRING, max_header=int(m.group(1)), max_body=int(m.group(2)), n=int(m.group(3)), k=0)
+    m = re.fullmatch(r"\s*CountSubstringOccurrences\(\s*(\d+)\s*,\s*(\d+)\s*\)\s*", arg)
+    if m:   # utils/array.circom:226
+        return dict(main_kind=zkwg.MAIN_COUNT_SUBSTRING, max_header=int(m.group(1)), max_body=int(m.group(2)), n=0, k=0)
     text = open(arg).read() if os.path.exists(arg) else arg
     kw = json.loads(text)
     base = os.path.dirname(arg) if os.path.exists(arg) else "."

@@ -577,6 +577,100 @@ def select_regex_reveal(g, pre, in_, start, max_reveal):
     return prev[:max_reveal]
 
 
+# ------------------------------------------------------------------ substring helpers
+def select_sub_array(g, pre, in_, start, length, max_sub):
+    """SelectSubArray(n, max_sub) (utils/array.circom:78-101) with its VarShiftLeft(n, max_sub) (:112-143) -> out wires"""
+    n = len(in_)
+    bl = log2ceil(n)
+    tmp = g.arr(pre + ".shifter.tmp", bl * n)
+    bits = g.num2bits(pre + ".shifter.n2b", start, bl)
+    prev = list(in_)
+    for j in range(bl):
+        cur = [wire(tmp[j * n + i]) for i in range(n)]
+        for i in range(n):
+            off = (i + (1 << j)) % n
+            g.cons.append((bits[j], lc_add(prev[off], prev[i], -1), lc_add(cur[i], prev[i], -1)))
+        prev = cur
+    lg = log2ceil(max_sub)
+    out = g.arr(pre + ".out", max_sub)
+    for i in range(max_sub):
+        # GreaterThan(lg)([length, i]) = LessThan(lg)(i, length)
+        gt = g.less_than(f"{pre}.gts[{i}].lt", lg, const(i), length)
+        g.cons.append((gt, prev[i], wire(out[i])))
+    return [wire(o) for o in out]
+
+
+def check_substring_match(g, pre, in_, sub):
+    """CheckSubstringMatch(S) (utils/array.circom:196-217) -> isMatch; 4 S + 3 constraints"""
+    g.lin(g.iszero(pre + ".anon_IsZero", sub[0]))            # firstElementNonZero === 0
+    acc = const(1)
+    for j in range(len(sub)):
+        d = wire(g.s(f"{pre}.difference[{j}]"))
+        g.cons.append((lc_add(in_[j], sub[j], -1), sub[j], d))
+        z = g.iszero(f"{pre}.anon_IsZero[{j}]", d)
+        nxt = wire(g.s(f"{pre}.matchAccumulator[{j + 1}]"))
+        g.cons.append((acc, z, nxt))
+        acc = nxt
+    return acc
+
+
+def count_substring_occurrences(g, pre, in_, sub):
+    """CountSubstringOccurrences(n, S) (utils/array.circom:226-254) -> count (a linear combination: summer = CalculateTotal)"""
+    n, S = len(in_), len(sub)
+    count = {}
+    for i in range(n):
+        window = [in_[i + j] if i + j < n else {} for j in range(S)]
+        count = lc_add(count, check_substring_match(g, f"{pre}.matches[{i}]", window, sub))
+    return count
+
+
+def reveal_substring(g, pre, in_, start, length, max_sub, check_uniqueness):
+    """RevealSubstring(n, max_sub, check_uniqueness) (helpers/reveal-substring.circom:13-50) -> substring wires"""
+    n = len(in_)
+    for name, bits, a, b in ((".anon_LessThan_start", log2ceil(n), start, const(n)),
+                             (".anon_LessThan_length", log2ceil(max_sub + 1), length, const(max_sub + 1)),
+                             (".anon_LessThan_sum", log2ceil(n + 1), lc_add(start, length), const(n + 1))):
+        g.lin(lc_add(g.less_than(pre + name, bits, a, b), const(-1)))     # === 1
+    out = select_sub_array(g, pre + ".selectSubArray", in_, start, length, max_sub)
+    if check_uniqueness:
+        g.lin(lc_add(count_substring_occurrences(g, pre + ".countSubstringOccurrences", in_, out), const(-1)))   # count === 1
+    return out
+
+
+def reveal_substring_constraint_count(n, max_sub, check_uniqueness):
+    """constraints reveal_substring_main_constraints emits"""
+    lt = lambda b: b + 1 + 1                      # Num2Bits(b + 1): b + 1 booleans, one sum
+    c = lt(log2ceil(n)) + lt(log2ceil(max_sub + 1)) + lt(log2ceil(n + 1)) + 3
+    c += log2ceil(n) + 1 + log2ceil(n) * n        # VarShiftLeft: n2b, tmp
+    c += max_sub * (lt(log2ceil(max_sub)) + 1)    # gts, out
+    if check_uniqueness:
+        c += n * (4 * max_sub + 3) + 1
+    return c + max_sub                            # substring <== selectSubArray.out
+
+
+def reveal_substring_main_constraints(symbols, n, max_sub, check_uniqueness):
+    """`component main = RevealSubstring(n, max_sub, check_uniqueness)` (tests/test-circuits/reveal-substring-test.circom:5)"""
+    slot_of = {nm: s for s, nm in symbols}
+    g = RsaBuilder(slot_of, "main")
+    in_ = [wire(slot_of[f"main.in[{i}]"]) for i in range(n)]
+    out = reveal_substring(g, "main", in_, wire(slot_of["main.substringStartIndex"]), wire(slot_of["main.substringLength"]),
+                           max_sub, check_uniqueness)
+    for i in range(max_sub):
+        g.lin(lc_add(wire(slot_of[f"main.substring[{i}]"]), out[i], -1))
+    return g.cons
+
+
+def count_substring_main_constraints(symbols, n, max_sub):
+    """`component main = CountSubstringOccurrences(n, max_sub)` (tests/test-circuits/count-substring-occurrences-test.circom:5):
+    n (4 max_sub + 3) + 1 constraints"""
+    slot_of = {nm: s for s, nm in symbols}
+    g = RsaBuilder(slot_of, "main")
+    in_ = [wire(slot_of[f"main.in[{i}]"]) for i in range(n)]
+    sub = [wire(slot_of[f"main.substring[{j}]"]) for j in range(max_sub)]
+    g.lin(lc_add(wire(slot_of["main.count"]), count_substring_occurrences(g, "main", in_, sub), -1))
+    return g.cons
+
+
 def base64_lookup(g, pre, x):
     le_Z = g.less_than(pre + ".le_Z", 8, x, const(91))
     ge_A = g.less_than(pre + ".ge_A.lt", 8, const(64), x)
@@ -908,8 +1002,12 @@ def _main():
     import argparse
     import zkwg
     ap = argparse.ArgumentParser(description=__doc__.split("\n\n")[0])
-    ap.add_argument("--main", choices=["email-verifier", "sha256-bytes", "rsa-verifier"], default="email-verifier",
-                    help="main component (tests/test-circuits/{email-verifier,sha,rsa}-test.circom)")
+    ap.add_argument("--main", choices=["email-verifier", "sha256-bytes", "rsa-verifier", "reveal-substring", "count-substring"],
+                    default="email-verifier",
+                    help="main component (tests/test-circuits/{email-verifier,sha,rsa,reveal-substring,count-substring-occurrences}-test.circom)")
+    ap.add_argument("--max-length", type=int, default=256, help="reveal-substring / count-substring: maxLength / maxLen")
+    ap.add_argument("--max-substring", type=int, default=16, help="reveal-substring / count-substring: maxSubstringLength / maxSubstringLen")
+    ap.add_argument("--check-uniqueness", type=int, default=1, choices=[0, 1], help="reveal-substring: shouldCheckUniqueness")
     ap.add_argument("--max-header", type=int, default=1024)
     ap.add_argument("--max-body", type=int, default=1536)
     ap.add_argument("--ignore-body-hash-check", type=int, default=0)
@@ -929,6 +1027,16 @@ def _main():
         c = zkwg.Circuit(zkwg.MAIN_RSA_VERIFIER, max_header=0, max_body=0, device=-1)
         sym = c.symbols()
         data = write_r1cs(len(sym), rsa_main_constraints(sym), n_pub_out=0, n_pub_in=17, n_prv_in=34)
+    elif a.main == "reveal-substring":
+        c = zkwg.Circuit(zkwg.MAIN_REVEAL_SUBSTRING, max_header=a.max_length, max_body=a.max_substring, n=a.check_uniqueness, k=0, device=-1)
+        sym = c.symbols()
+        data = write_r1cs(len(sym), reveal_substring_main_constraints(sym, a.max_length, a.max_substring, a.check_uniqueness),
+                          n_pub_out=a.max_substring, n_pub_in=0, n_prv_in=a.max_length + 2)
+    elif a.main == "count-substring":
+        c = zkwg.Circuit(zkwg.MAIN_COUNT_SUBSTRING, max_header=a.max_length, max_body=a.max_substring, n=0, k=0, device=-1)
+        sym = c.symbols()
+        data = write_r1cs(len(sym), count_substring_main_constraints(sym, a.max_length, a.max_substring),
+                          n_pub_out=1, n_pub_in=0, n_prv_in=a.max_length + a.max_substring)
     else:
         c = zkwg.Circuit(zkwg.MAIN_EMAIL_VERIFIER, max_header=a.max_header, max_body=a.max_body, device=-1,
                          ignore_body_hash_check=a.ignore_body_hash_check,
