@@ -583,7 +583,9 @@ int zkwg_zkey_check(const uint8_t* zkey, uint64_t zkey_len, uint64_t* n_vars, ui
  * the compiler's own `.r1cs`, the file a zkey is keyed to: every wire of every combination is substituted by the kept-v1
  * signal(s) it derives from) is attached to the handle once -- BEFORE the
  * first zkwg_scratch_bytes / zkwg_prepare_device call that should serve it, the compact image grows by the results of the
- * combinations that are genuine sums -- and zkwg_expand_abc_device then writes A.w | B.w | C.w (3 * nConstraints values,
+ * combinations that are genuine sums, and only a prepare that follows the attachment writes the SHA-256 trace words the
+ * descriptors name (an EmailVerifier handle without a system keeps round records alone, csrc/zkwg_sha_rounds.h): a batch
+ * prepared before the attachment needs a fresh zkwg_prepare_device -- and zkwg_expand_abc_device then writes A.w | B.w | C.w (3 * nConstraints values,
  * `abc_stride` >= zkwg_abc_bytes apart) of emails [first, first + count) straight from the prepared image: a combination
  * that is one wire is written like that wire, sums of bits and small integers are 64-bit integer rows, only the rest is
  * arithmetic mod r.  Bit-identical to zkwg_r1cs_evaluate_device on the expanded witness (montgomery = 1: to that of the
@@ -865,6 +867,11 @@ enum zkwg_segment_type {
   ZKWG_SEG_SMALL = 0,    /* small[src + r]                                                            */
   ZKWG_SEG_FR = 1,       /* fr[src + r]                                                               */
   ZKWG_SEG_BITS = 2,     /* groups of a bits in b words: bit (r % a) of bits[src + (r / a) * b ...]    */
+  /* types 3-5 and the ZKWG_SEG_BITS segment (a = 33, b = 1) that follows them cover one Sha256compression; its 952 words at src
+   * are the block's TRACE.  EmailVerifier handles: c = first word in `small` of the block's 200-word round record (W[0..63],
+   * A[-4..63], E[-4..63]: csrc/zkwg_sha_rounds.h states how every group derives from it), which is what zk_expand decodes; the
+   * trace words are written only by a prepare of a handle created with zkwg_circuit_create_full or with a constraint system
+   * attached.  Sha256Bytes handles: c = 0, no record, the trace is always written. */
   ZKWG_SEG_SHA_SP = 3,   /* 162-slot periods over 5 words (32,32,32,32,34 bits): SigmaPlus instances  */
   ZKWG_SEG_SHA_T1 = 4,   /* 131-slot periods over 4 words (32,32,32,35): T1 instances                 */
   ZKWG_SEG_SHA_T2 = 5,   /* 161-slot periods over 5 words (32,32,32,32,33): T2 instances              */

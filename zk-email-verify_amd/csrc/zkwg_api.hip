@@ -666,7 +666,17 @@ int zkwg_image_layout(const zkwg_circuit_t* c, uint64_t n, zkwg_image_layout_t* 
 uint64_t zkwg_segment_table(const zkwg_circuit_t* c, zkwg_segment* out, uint64_t cap) {
   if (!c) return 0;
   static_assert(sizeof(zkwg_segment) == sizeof(ZkSeg), "public segment struct must mirror ZkSeg");
-  if (out) memcpy(out, c->segs.data(), std::min<u64>(cap, c->segs.size()) * sizeof(ZkSeg));
+  const u64 n = std::min<u64>(cap, c->segs.size());
+  if (out) memcpy(out, c->segs.data(), n * sizeof(ZkSeg));
+  // the record-decoded SHA types are reported as the documented trace-decoded ones (same src, a, b; c = the round record)
+  for (u64 i = 0; out && i < n; ++i)
+    switch (out[i].type) {
+      case ZSEG_SHAR_SP: out[i].type = ZSEG_SHA_SP; break;
+      case ZSEG_SHAR_T1: out[i].type = ZSEG_SHA_T1; break;
+      case ZSEG_SHAR_T2: out[i].type = ZSEG_SHA_T2; break;
+      case ZSEG_SHAR_SUM: out[i].type = ZSEG_BITS; break;
+      default: break;
+    }
   return c->segs.size();
 }
 uint32_t zkwg_inverse_table_half(const zkwg_circuit_t* c) { return c ? c->s.inv_half : 0; }
@@ -962,7 +972,11 @@ int zkwg_prepare_device(zkwg_circuit_t* c, const void* d_in, uint64_t n, void* d
   if (tm) hipEventRecord(evs[++ki], st);
   if (s.nframes && (pm & 2u)) {
     u64 units = (u64)ne * s.total_blocks;
-    hipLaunchKernelGGL(zk_sha_trace, dim3((u32)((units + 63) / 64)), dim3(64), 0, st, s, B);
+    // EmailVerifier: round records; the trace only for the readers that address its words (descriptor tables)
+    const dim3 g((u32)((units + 63) / 64));
+    if (s.fr[0].m_rounds == ~0u) hipLaunchKernelGGL((zk_sha_trace<false, true>), g, dim3(64), 0, st, s, B);
+    else if (c->full_W || c->abc_m) hipLaunchKernelGGL((zk_sha_trace<true, true>), g, dim3(64), 0, st, s, B);
+    else hipLaunchKernelGGL((zk_sha_trace<true, false>), g, dim3(64), 0, st, s, B);
   }
   if (tm) hipEventRecord(evs[++ki], st);
   if (s.net_mode) {

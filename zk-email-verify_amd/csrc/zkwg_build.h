@@ -114,6 +114,7 @@ static bool build_sched(const zkwg_config& cfg, ZkSched& s, std::vector<ZkSeg>& 
       s.nframes = s.body ? 2 : 1;
       init_frame(s.fr[0], cfg.max_header, 0, s.in_off[ZKWG_IN_HEADER], s.in_off[ZKWG_IN_HEADER_LEN]);
       if (s.body) init_frame(s.fr[1], cfg.max_body, 1, s.in_off[ZKWG_IN_BODY], s.in_off[ZKWG_IN_BODY_LEN]);
+      w.sha_rounds = true;   // the flagship's image: 800 bytes of round states per SHA block instead of the 7,616-byte trace
       zk_walk_main_ev(w, s);
       max_small = std::max<u64>(max_small, 2100);
       max_small = std::max<u64>(max_small, (u64)cfg.max_header + 64);

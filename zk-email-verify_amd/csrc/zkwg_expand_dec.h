@@ -12,6 +12,7 @@
 #include "zkwg_dev.h"
 #include "zkwg_bh_dfa.h"
 #include "zkwg_net_core.h"
+#include "zkwg_sha_rounds.h"
 
 // the decoders also run on the host (zkwg_expand_host: witnesses expanded in host memory from a downloaded image)
 #define ZK_DEC __host__ __device__
@@ -68,6 +69,18 @@ struct ZkDecSha {
     const u32 i = r / PER, q = r - i * PER;
     const u32 sub = zk_minu(q >> 5, WORDS - 1u);
     return (u32)(p[i * WORDS + sub] >> (q - sub * 32u)) & 1u;
+  }
+};
+// the same periods (and the 136 sums of 33 bits) of an EmailVerifier handle, recomputed from the block's round record (zkwg_sha_rounds.h)
+template <u32 TYPE>
+struct ZkDecShaR {
+  const u32* __restrict__ p;
+  ZK_DEC ZkDecShaR(const ZkSeg& sg, const ZkCtx& cx) : p(cx.small + sg.c) {}
+  ZK_DEC u32 operator()(u32 r) const {
+    if constexpr (TYPE == ZSEG_SHAR_SP) return zk_shar_sp(p, r);
+    else if constexpr (TYPE == ZSEG_SHAR_T1) return zk_shar_t1(p, r);
+    else if constexpr (TYPE == ZSEG_SHAR_T2) return zk_shar_t2(p, r);
+    else return zk_shar_sum(p, r);
   }
 };
 struct ZkDecIsz {
@@ -333,7 +346,9 @@ struct ZkDecSubm {
   X(ZSEG_SHA_T2, ZkDecSha<ZK_T2_SLOTS ZK_COMMA 5>) X(ZSEG_ISZ, ZkDecIsz) X(ZSEG_SEL, ZkDecSel) X(ZSEG_IN8, ZkDecIn8)   \
   X(ZSEG_IN8MASK, ZkDecIn8Mask) X(ZSEG_IN8BITS, ZkDecIn8Bits) X(ZSEG_LIMB, ZkDecLimb) X(ZSEG_LTBITS, ZkDecLtBits)      \
   X(ZSEG_REGSEL, ZkDecRegSel) X(ZSEG_VSHIFT, ZkDecVShift) X(ZSEG_B64BITS, ZkDecB64<false>) X(ZSEG_B64, ZkDecB64<true>) \
-  X(ZSEG_DFA, ZkDecDfa) X(ZSEG_RSLB, ZkDecRslb) X(ZSEG_NETP, ZkDecNetP) X(ZSEG_NETQ, ZkDecNetQ)
+  X(ZSEG_DFA, ZkDecDfa) X(ZSEG_RSLB, ZkDecRslb) X(ZSEG_NETP, ZkDecNetP) X(ZSEG_NETQ, ZkDecNetQ)                         \
+  X(ZSEG_SHAR_SP, ZkDecShaR<ZSEG_SHAR_SP>) X(ZSEG_SHAR_T1, ZkDecShaR<ZSEG_SHAR_T1>) X(ZSEG_SHAR_T2, ZkDecShaR<ZSEG_SHAR_T2>) \
+  X(ZSEG_SHAR_SUM, ZkDecShaR<ZSEG_SHAR_SUM>)
 #define ZK_COMMA ,
 // ZSEG_SUBM stays out of the common switch: zk_expand3's register budget (64 VGPRs, 8 wavefronts per SIMD) and rate are held as they
 // are; the substring mains expand through their own instantiation (SUBM = true: zk_expand3_subm, the host expansion)

@@ -5,7 +5,7 @@
 #include "zkwg_o0.h"
 
 __global__ void zk_sha_chain(ZkSched s, ZkBufs B);   // zkwg_kernels_sha.hip
-__global__ void zk_sha_trace(ZkSched s, ZkBufs B);   // zkwg_kernels_sha.hip
+template <bool REC, bool TRACE> __global__ void zk_sha_trace(ZkSched s, ZkBufs B);   // zkwg_kernels_sha.hip: <records, trace> = <0,1>, <1,0>, <1,1>
 __global__ void zk_rsa(ZkSched s, ZkBufs B);         // zkwg_kernels_rsa.hip
 __global__ void zk_fpmul_small(ZkSched s, ZkBufs B);
 __global__ void zk_substr(ZkSched s, ZkBufs B);      // zkwg_kernels_substr.hip

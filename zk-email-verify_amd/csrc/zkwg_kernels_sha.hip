@@ -4,14 +4,16 @@
 //   zk_sha_chain   native SHA-256 chaining state of every block, one lane per
 //                  (email, frame); also the frame-level scalars (inBlockIndex, selector
 //                  index, selected digest, LessEqThan input) and the frame's assertions.
-//   zk_sha_trace   one lane per (email, SHA block): the 952 bit-groups that make up the
-//                  30,952 kept signals of circomlib's Sha256compression for that block.
+//   zk_sha_trace   one lane per (email, SHA block): the round states (and, for the readers
+//                  that need them, the 952 bit-groups) behind the 30,952 kept signals of
+//                  circomlib's Sha256compression for that block.
 //
 // Reference gate sequence: packages/circuits/lib/sha.circom:17-38 (Sha256Bytes), :47-80
 // (Sha256BytesPartial), :89-203 (Sha256General), :212-292 (Sha256Partial) and circomlib
 // sha256compression.
 #include "zkwg_dev.h"
 #include "zkwg_kernels.h"
+#include "zkwg_sha_rounds.h"
 
 // ------------------------------------------------------------------ chain
 __global__ __launch_bounds__(64) void zk_sha_chain(ZkSched s, ZkBufs B) {
@@ -88,8 +90,9 @@ __global__ __launch_bounds__(64) void zk_sha_chain(ZkSched s, ZkBufs B) {
 }
 
 // ------------------------------------------------------------------ trace
-// One u64 per kept bit-group; bit k of a group = the signal with index k (circomlib bit
-// vectors are LSB-first).  Group order = layout order inside the block (zkwg_sched.h).
+// The block's assertions, then its 64 rounds (zkwg_sha_rounds.h): REC: the 200-word round record zk_expand decodes the
+// block's slots from; TRACE: the 952 groups, one u64 per kept bit-group.
+template <bool REC, bool TRACE>
 __global__ __launch_bounds__(64) void zk_sha_trace(ZkSched s, ZkBufs B) {
   const u64 unit = (u64)blockIdx.x * blockDim.x + threadIdx.x;
   const u32 e = (u32)(unit / s.total_blocks);
@@ -132,42 +135,11 @@ __global__ __launch_bounds__(64) void zk_sha_trace(ZkSched s, ZkBufs B) {
     for (int t = 0; t < 64; ++t) bad = bad || (mk[t] > 1);
     if (bad) B.status[e] = 4;
   }
-#pragma unroll
-  for (int t = 16; t < 64; ++t) {  // sigmaPlus[t-16]
-    u32 x2 = w[t - 2], x15 = w[t - 15];
-    u32 a1 = zk_rotr(x2, 17), b1 = zk_rotr(x2, 19), c1 = x2 >> 10;
-    u32 a0 = zk_rotr(x15, 7), b0 = zk_rotr(x15, 18), c0 = x15 >> 3;
-    u32 s1 = a1 ^ b1 ^ c1, s0 = a0 ^ b0 ^ c0;
-    u64 sum = (u64)s1 + w[t - 7] + s0 + w[t - 16];
-    u64* g = tr + ZK_G_SP + (t - 16) * 5;
-    g[0] = s1; g[1] = b1 & c1; g[2] = s0; g[3] = b0 & c0; g[4] = sum;
-    w[t] = (u32)sum;
-  }
-  const u32 h0 = hin[0], h1 = hin[1], h2 = hin[2], h3 = hin[3], h4 = hin[4], h5 = hin[5], h6 = hin[6], h7 = hin[7];
-  u32 a = h0, b = h1, c = h2, d = h3, e_ = h4, f_ = h5, g_ = h6, h = h7;
-#pragma unroll
-  for (int t = 0; t < 64; ++t) {
-    u32 eb = zk_rotr(e_, 11), ec = zk_rotr(e_, 25);
-    u32 bs1 = zk_rotr(e_, 6) ^ eb ^ ec;
-    u32 ch = (e_ & f_) ^ (~e_ & g_);
-    u64 t1 = (u64)h + bs1 + ch + ZK_K256[t] + w[t];
-    u64* g1 = tr + ZK_G_T1 + t * 4;
-    g1[0] = ch; g1[1] = bs1; g1[2] = eb & ec; g1[3] = t1;
-    u32 ab = zk_rotr(a, 13), ac = zk_rotr(a, 22);
-    u32 bs0 = zk_rotr(a, 2) ^ ab ^ ac;
-    u32 mmid = b & c;
-    u32 maj = (a & (b ^ c)) | mmid;
-    u64 t2 = (u64)bs0 + maj;
-    u64* g2 = tr + ZK_G_T2 + t * 5;
-    g2[0] = bs0; g2[1] = ab & ac; g2[2] = maj; g2[3] = mmid; g2[4] = t2;
-    u64 sume = (u64)d + (u32)t1;
-    u64 suma = (u64)(u32)t1 + (u32)t2;
-    tr[ZK_G_SUMA + t] = suma;
-    tr[ZK_G_SUME + t] = sume;
-    h = g_; g_ = f_; f_ = e_; e_ = (u32)sume; d = c; c = b; b = a; a = (u32)suma;
-  }
-  tr[ZK_G_FSUM + 0] = (u64)h0 + a; tr[ZK_G_FSUM + 1] = (u64)h1 + b;
-  tr[ZK_G_FSUM + 2] = (u64)h2 + c; tr[ZK_G_FSUM + 3] = (u64)h3 + d;
-  tr[ZK_G_FSUM + 4] = (u64)h4 + e_; tr[ZK_G_FSUM + 5] = (u64)h5 + f_;
-  tr[ZK_G_FSUM + 6] = (u64)h6 + g_; tr[ZK_G_FSUM + 7] = (u64)h7 + h;
+  u32* rec = REC ? B.small + (u64)e * s.img_small + f.m_rounds + blk * ZK_SHAR_WORDS : nullptr;
+  zk_sha_rounds<REC, TRACE>(w, hin, rec, tr);
 }
+// what a handle's image needs (zkwg_api.hip zkwg_prepare_device): the trace alone (Sha256Bytes main), the records alone
+// (EmailVerifier), or both (EmailVerifier with a descriptor consumer: a numbered circuit, an attached constraint system)
+template __global__ void zk_sha_trace<false, true>(ZkSched s, ZkBufs B);
+template __global__ void zk_sha_trace<true, false>(ZkSched s, ZkBufs B);
+template __global__ void zk_sha_trace<true, true>(ZkSched s, ZkBufs B);

@@ -17,6 +17,7 @@
 #include <vector>
 #include <functional>
 #include "zkwg_sched.h"
+#include "zkwg_sha_rounds.h"
 #include "zkwg_bh_dfa.h"
 #include "zkwg_circom.h"
 
@@ -25,6 +26,7 @@ struct ZkWalker {
   u64 cur = 0;        // next free slot (advanced by one/arr/skip)
   u64 seg_cur = 0;    // next slot not yet covered by a segment (advanced by seg)
   bool names = false; // emit names?
+  bool sha_rounds = false;   // SHA frames get round records and their compressions the record-decoded segment types (EmailVerifier)
   std::function<void(u64 slot, const std::string& name)> sink;
   std::vector<ZkSeg> segs;
   u32 nbits = 0, nsmall = 0, nfr = 0;
@@ -66,12 +68,14 @@ static inline u32 zk_log2ceil(u64 a) {  // utils/functions.circom:7-17
 
 static inline std::string zk_idx(const std::string& base, u32 i) { return base + "[" + std::to_string(i) + "]"; }
 
-// circomlib Sha256compression: ZK_COMP_SLOTS kept signals, 952 image words at `src`
-static inline void zk_walk_compression(ZkWalker& w, const std::string& p, u32 src) {
-  w.seg(ZSEG_SHA_SP, 48 * ZK_SP_SLOTS, src + ZK_G_SP);
-  w.seg(ZSEG_SHA_T1, 64 * ZK_T1_SLOTS, src + ZK_G_T1);
-  w.seg(ZSEG_SHA_T2, 64 * ZK_T2_SLOTS, src + ZK_G_T2);
-  w.seg(ZSEG_BITS, 136 * 33, src + ZK_G_SUMA, 33, 1);
+// circomlib Sha256compression: ZK_COMP_SLOTS kept signals, 952 image words at `src`; rec != 0xffffffff: the block's round
+// record in `small`, which the slots are then decoded from (zkwg_sha_rounds.h)
+static inline void zk_walk_compression(ZkWalker& w, const std::string& p, u32 src, u32 rec) {
+  const bool r = rec != ~0u;
+  w.seg(r ? ZSEG_SHAR_SP : ZSEG_SHA_SP, 48 * ZK_SP_SLOTS, src + ZK_G_SP, 0, 0, r ? rec : 0);
+  w.seg(r ? ZSEG_SHAR_T1 : ZSEG_SHA_T1, 64 * ZK_T1_SLOTS, src + ZK_G_T1, 0, 0, r ? rec : 0);
+  w.seg(r ? ZSEG_SHAR_T2 : ZSEG_SHA_T2, 64 * ZK_T2_SLOTS, src + ZK_G_T2, 0, 0, r ? rec : 0);
+  w.seg(r ? ZSEG_SHAR_SUM : ZSEG_BITS, 136 * 33, src + ZK_G_SUMA, 33, 1, r ? rec : 0);
   if (!w.names) { w.skip(ZK_COMP_SLOTS); return; }
   for (u32 i = 0; i < 48; ++i) {
     std::string q = zk_idx(p + ".sigmaPlus", i);
@@ -103,6 +107,11 @@ static inline void zk_alloc_sha_frame(ZkWalker& w, ZkShaFrame& f) {
   f.b_lenbits = w.alloc_bits(1);
   f.b_digest = w.alloc_bits(4);
   f.b_trace = w.alloc_bits(f.nblocks * ZK_TRACE_GROUPS);
+  f.m_rounds = ~0u;
+  if (w.sha_rounds) {
+    w.alloc_small((4u - (w.nsmall & 3u)) & 3u);   // 16-byte aligned records (the image's small words per email are a multiple of 4)
+    f.m_rounds = w.alloc_small(f.nblocks * ZK_SHAR_WORDS);
+  }
 }
 
 // Sha256Bytes / Sha256BytesPartial sub-tree (lib/sha.circom:17-38, 47-80, 89-292)
@@ -113,7 +122,8 @@ static inline void zk_walk_sha_frame(ZkWalker& w, const std::string& p, const Zk
   w.seg(ZSEG_BITS, f.lenbits + 1, f.b_lenbits, f.lenbits + 1, 1);
   w.arr(sha + ".bitLengthVerifier.lt.n2b.out", f.lenbits + 1);
   for (u32 i = 0; i < f.nblocks; ++i)
-    zk_walk_compression(w, zk_idx(sha + ".sha256compression", i), f.b_trace + i * ZK_TRACE_GROUPS);
+    zk_walk_compression(w, zk_idx(sha + ".sha256compression", i), f.b_trace + i * ZK_TRACE_GROUPS,
+                        f.m_rounds == ~0u ? ~0u : f.m_rounds + i * ZK_SHAR_WORDS);
   w.seg(ZSEG_SEL, (u64)256 * 3 * f.nblocks, f.m_idx, f.nblocks, f.m_digest);
   if (!w.names) {
     w.skip((u64)256 * 3 * f.nblocks);

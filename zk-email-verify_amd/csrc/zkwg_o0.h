@@ -72,6 +72,7 @@ static inline bool zk_slot_range(const ZkSeg& g, u32 r, long long& lo, long long
   lo = 0; hi = 1;
   switch (g.type) {
     case ZSEG_BITS: case ZSEG_SHA_SP: case ZSEG_SHA_T1: case ZSEG_SHA_T2: case ZSEG_IN8BITS: case ZSEG_LTBITS: case ZSEG_B64BITS:
+    case ZSEG_SHAR_SP: case ZSEG_SHAR_T1: case ZSEG_SHAR_T2: case ZSEG_SHAR_SUM:
       return true;
     case ZSEG_IN8: hi = 255; return true;
     case ZSEG_IN8MASK: hi = 255 * 255; return true;
@@ -102,10 +103,11 @@ static inline void zk_o0_slot_desc(const std::vector<ZkSeg>& segs, u64 slot, u32
   if (slot == 0) { out[0] = ZK_D_IMM << 28; out[1] = 1; return; }   // wire 0 of every circom witness: the constant 1 (the constant term of a combination)
   auto bit64 = [&](u32 word, u32 sh) { out[0] = (ZK_D_BIT64 << 28) | sh; out[1] = word; };
   switch (g.type) {
-    case ZSEG_BITS: { const u32 grp = r / g.a, bit = r % g.a; bit64(g.src + grp * g.b + (bit >> 6), bit & 63u); return; }
-    case ZSEG_SHA_SP: { const u32 i = r / ZK_SP_SLOTS, q = r % ZK_SP_SLOTS, sub = std::min(q >> 5, 4u); bit64(g.src + i * 5 + sub, q - sub * 32); return; }
-    case ZSEG_SHA_T1: { const u32 i = r / ZK_T1_SLOTS, q = r % ZK_T1_SLOTS, sub = std::min(q >> 5, 3u); bit64(g.src + i * 4 + sub, q - sub * 32); return; }
-    case ZSEG_SHA_T2: { const u32 i = r / ZK_T2_SLOTS, q = r % ZK_T2_SLOTS, sub = std::min(q >> 5, 4u); bit64(g.src + i * 5 + sub, q - sub * 32); return; }
+    // (the record-decoded SHA types: a descriptor names the trace word, which zk_sha_trace writes for handles that have descriptors)
+    case ZSEG_BITS: case ZSEG_SHAR_SUM: { const u32 grp = r / g.a, bit = r % g.a; bit64(g.src + grp * g.b + (bit >> 6), bit & 63u); return; }
+    case ZSEG_SHA_SP: case ZSEG_SHAR_SP: { const u32 i = r / ZK_SP_SLOTS, q = r % ZK_SP_SLOTS, sub = std::min(q >> 5, 4u); bit64(g.src + i * 5 + sub, q - sub * 32); return; }
+    case ZSEG_SHA_T1: case ZSEG_SHAR_T1: { const u32 i = r / ZK_T1_SLOTS, q = r % ZK_T1_SLOTS, sub = std::min(q >> 5, 3u); bit64(g.src + i * 4 + sub, q - sub * 32); return; }
+    case ZSEG_SHA_T2: case ZSEG_SHAR_T2: { const u32 i = r / ZK_T2_SLOTS, q = r % ZK_T2_SLOTS, sub = std::min(q >> 5, 4u); bit64(g.src + i * 5 + sub, q - sub * 32); return; }
     case ZSEG_IN8BITS: out[0] = (ZK_D_BIT8 << 28) | (r & 7u); out[1] = g.src + (r >> 3); return;
     case ZSEG_IN8: out[0] = ZK_D_BYTE << 28; out[1] = g.src + r; return;
     case ZSEG_SMALL: out[0] = ZK_D_SMALLRAW << 28; out[1] = g.src + r; return;

@@ -60,7 +60,12 @@ enum ZkSegType : u32 {
                     // 4 S + 2 slots: matchAccumulator[1..S], difference[S], IsZero(substring[0]) (out, inv), S x IsZero(difference[j]) (out, inv);
                     // in[] = record bytes at src, substring = small[b .. b + S), leading-match lengths = small[b + S .. b + S + c)
                     // (decoded by ZkDecSubm, which only zk_expand3_subm and the host expansion instantiate: zkwg_kernels_substr.hip)
-  ZSEG_NTYPES = 24
+  // Sha256compression signals decoded from the block's round record (zkwg_sha_rounds.h; EmailVerifier handles): c = the record's
+  // first word in `small`; src (and a, b of the sums) still name the block's trace words as in ZSEG_SHA_SP / _T1 / _T2 / ZSEG_BITS(33, 1),
+  // which exist only for a handle with a descriptor consumer (zkwg_o0.h) -- the public segment table reports those four types
+  ZSEG_SHAR_SP = 24, ZSEG_SHAR_T1 = 25, ZSEG_SHAR_T2 = 26,
+  ZSEG_SHAR_SUM = 27,  // suma[64], sume[64], fsum[8]: 136 x 33 slots
+  ZSEG_NTYPES = 28
 };
 
 // ZSEG_RSLB kinds (helpers/remove-soft-line-breaks.circom:14-126); enc = the emailBody bytes at src
@@ -101,6 +106,7 @@ ZK_HD bool zk_seg_is_immediate(const ZkSeg& g) {
   switch (g.type) {
     case ZSEG_BITS: case ZSEG_SHA_SP: case ZSEG_SHA_T1: case ZSEG_SHA_T2: case ZSEG_IN8: case ZSEG_IN8MASK:
     case ZSEG_IN8BITS: case ZSEG_LTBITS: case ZSEG_B64BITS: case ZSEG_HOLE: return true;
+    case ZSEG_SHAR_SP: case ZSEG_SHAR_T1: case ZSEG_SHAR_T2: case ZSEG_SHAR_SUM: return true;
     case ZSEG_DFA: return g.a != ZDFA_EQ;
     case ZSEG_RSLB: return g.a != ZRS_EQ;
     default: return false;
@@ -139,7 +145,8 @@ struct ZkShaFrame {      // one Sha256Bytes / Sha256BytesPartial instance
   u32 hstate_base;       // first chaining-state index (units of 8 x u32) in scratch
   u32 block_base;        // index of this frame's first block among the email's blocks
   // image offsets
-  u32 b_trace;           // bits: nblocks x ZK_TRACE_GROUPS words
+  u32 b_trace;           // bits: nblocks x ZK_TRACE_GROUPS words (written for the Sha256Bytes main and for descriptor consumers: zkwg_sha_rounds.h)
+  u32 m_rounds;          // small: nblocks x ZK_SHAR_WORDS words, one round record per block, 16-byte aligned (0xffffffff = absent: Sha256Bytes main)
   u32 b_lenbits;         // bits: 1 word, the LessEqThan Num2Bits input
   u32 b_digest;          // bits: 4 words, selected hash as one LSB-first 256-bit group (bit k = out[k])
   u32 m_ibi;             // small: inBlockIndex
