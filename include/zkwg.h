@@ -58,7 +58,9 @@ extern "C" {
  * zkwg_scratch_bytes includes the Montgomery-copy area (and, round 5, 612 bytes per 16-byte body chunk of staging for the
  * removeSoftLineBreaks chunk hashes, behind the image arrays); zkwg_segment.pad is kernel-private.
  * Added since without breaking 2: zkwg_expand_host / zkwg_set_host_expand, zkwg_circuit_attach_r1cs / zkwg_expand_abc_device /
- * zkwg_expand_abc_host / zkwg_abc_bytes, ZKWG_MAIN_FP_MUL, ZKWG_MAIN_REVEAL_SUBSTRING, ZKWG_MAIN_COUNT_SUBSTRING. */
+ * zkwg_expand_abc_host / zkwg_abc_bytes, ZKWG_MAIN_FP_MUL, ZKWG_MAIN_REVEAL_SUBSTRING, ZKWG_MAIN_COUNT_SUBSTRING,
+ * ZKWG_MAIN_EMAIL_REVEAL with zkwg_app_config / zkwg_circuit_create_app and the record fields ZKWG_IN_SUBSTRING_START /
+ * ZKWG_IN_SUBSTRING_LEN (ZKWG_IN_NFIELDS = 15; they take no room in the records of the other mains). */
 #define ZKWG_ABI_VERSION 3
 
 /* `component main = ...` choices (the reference's own test mains). */
@@ -73,10 +75,14 @@ enum zkwg_main_kind {
                                    max_header = maxLength, max_body = maxSubstringLength, n = shouldCheckUniqueness (0 / 1), k = 0, every
                                    flag 0; 2 <= max_body < max_header <= 65536, neither needs to be a multiple of 64 (the record pads).
                                    in[] in ZKWG_IN_HEADER, substringStartIndex in ZKWG_IN_BODY_HASH_INDEX, substringLength in ZKWG_IN_BODY_LEN */
-  ZKWG_MAIN_COUNT_SUBSTRING = 5 /* CountSubstringOccurrences(maxLen, maxSubstringLen) (utils/array.circom:226-254,
+  ZKWG_MAIN_COUNT_SUBSTRING = 5,/* CountSubstringOccurrences(maxLen, maxSubstringLen) (utils/array.circom:226-254,
                                    count-substring-occurrences-test.circom:5: (1024, 128)).  max_header = maxLen, max_body =
                                    maxSubstringLen, n = k = 0; 2 <= max_body <= max_header <= 65536.  in[] in ZKWG_IN_HEADER, substring[] in
                                    ZKWG_IN_BODY.  Both mains: elements are bytes; no `.sym` layout, no Montgomery-form output (BAD_CONFIG) */
+  ZKWG_MAIN_EMAIL_REVEAL = 6    /* EmailReveal(maxHeader, maxBody, n, k, ignoreBodyHashCheck, revealFromBody, maxSubstringLength,
+                                   shouldCheckUniqueness, withNullifier), no public inputs (zk-email-verify_amd/circuits/email-reveal.circom):
+                                   EmailVerifier + RevealSubstring over the header or the body + PackBytes of the revealed bytes +
+                                   EmailNullifier(signature).  Created with zkwg_circuit_create_app only */
 };
 
 /* Witness layouts.  KEPT_V1 is the compact layout documented in DESIGN.md; SYM is KEPT_V1 re-ordered
@@ -111,7 +117,9 @@ enum zkwg_input_field {
   ZKWG_IN_BODY_MASK = 10,     /* u8[max_body]    bodyMask   (enable_body_masking)    */
   ZKWG_IN_DECODED_BODY = 11,  /* u8[max_body]    decodedEmailBodyIn (remove_soft_line_breaks) */
   ZKWG_IN_RANGE_FLAGS = 12,   /* u32 bit f = an element of field f did not fit its packed slot (generic path)  */
-  ZKWG_IN_NFIELDS = 13
+  ZKWG_IN_SUBSTRING_START = 13, /* u32 substringStartIndex (ZKWG_MAIN_EMAIL_REVEAL; absent from the records of the other mains) */
+  ZKWG_IN_SUBSTRING_LEN = 14,   /* u32 substringLength     (ZKWG_MAIN_EMAIL_REVEAL) */
+  ZKWG_IN_NFIELDS = 15
 };
 
 /* Per-email status: circom_runtime exception codes. */
@@ -189,6 +197,23 @@ typedef struct zkwg_regex_source {
 int zkwg_circuit_create_regex(const zkwg_config* cfg, int device, const zkwg_regex_source* regex,
                               const char* sym_text, uint64_t sym_len, const char* alias_text, uint64_t alias_len,
                               const uint8_t* r1cs, uint64_t r1cs_len, zkwg_circuit_t** out);
+/* Application main (ZKWG_MAIN_EMAIL_REVEAL): `cfg` as for EmailVerifier (n = 121, k = 17, max_header / max_body by its rules, every
+ * masking / soft-line-break flag 0), `app` what sits on top of it.  Public signals, all outputs: pubkeyHash, (with_nullifier)
+ * emailNullifier = Poseidon(1)(PoseidonLarge(121, 17)(signature)), revealed[ceil(max_substring / 31)] = the revealed bytes packed
+ * little-endian, 31 per field element (utils/bytes.circom:28-60).  Inputs: EmailVerifier's, then substringStartIndex
+ * (ZKWG_IN_SUBSTRING_START) and substringLength (ZKWG_IN_SUBSTRING_LEN), set with zkwg_pack_field or written as u32 at
+ * zkwg_input_offset.  Status 4 on anything EmailVerifier or RevealSubstring asserts and on a range flag (a source element that
+ * is not a byte, a start or length above 2^32 - 1).  Bounds: 2 <= max_substring < the source's maximum length;
+ * reveal_from_body = 1 needs the body-hash check; each flag 0 or 1.  No `.sym` / numbered layout, no attached constraint system,
+ * no Montgomery-form output, no regex template (BAD_CONFIG): proofs go through zkwg_prover_create_wtns.  zkwg_circuit_create
+ * refuses kind 6 with BAD_CONFIG (zkwg_last_error names this call). */
+typedef struct zkwg_app_config {
+  uint32_t reveal_from_body;   /* 0: RevealSubstring over emailHeader, 1: over emailBody */
+  uint32_t max_substring;      /* maxSubstringLength */
+  uint32_t check_uniqueness;   /* shouldCheckUniqueness: the match matrix of CountSubstringOccurrences is part of the circuit */
+  uint32_t with_nullifier;     /* the emailNullifier output and its two Poseidon instances */
+} zkwg_app_config;
+int zkwg_circuit_create_app(const zkwg_config* cfg, const zkwg_app_config* app, int device, zkwg_circuit_t** out);
 /* out[0..8): kept signals, temporaries, gates, assertion gates, chunks, 64-gate steps, LDS words that hold gate
  * values, gates on the evaluator's 64-bit path (handles created by zkwg_circuit_create_regex) */
 int zkwg_regex_info(const zkwg_circuit_t* c, uint64_t out[8]);
@@ -349,7 +374,7 @@ int zkwg_expand_device(zkwg_circuit_t* c, const void* d_packed_inputs, uint64_t 
 int zkwg_set_prepare_throttle(zkwg_circuit_t* c, int rsa_wavefronts_per_cu);
 /* Measurement aid (tools/beside.py): zkwg_prepare_device launches only the kernels whose bit is
  * set -- bit 0 zk_sha_chain, 1 zk_sha_trace, 2 zk_net_eval, 3 zk_misc_ev, 4 zk_rsa, 5 zk_poseidon9*, 6 zk_rslb_chunks,
- * 7 zk_rslb_chain, 8 the row kernels of numbered / constraint-attached handles.  Default 0xffffffff (everything); with a
+ * 7 zk_rslb_chain, 8 the row kernels of numbered / constraint-attached handles, 9 zk_app_tail (zk_substr shares bit 4).  Default 0xffffffff (everything); with a
  * partial mask the images of the batch are NOT complete, so only timing may be taken from such a call. */
 int zkwg_set_prepare_mask(zkwg_circuit_t* c, uint32_t kernel_mask);
 

@@ -26,7 +26,7 @@
 #include <atomic>
 #include <emmintrin.h>
 
-#define ZK_MAX_KERNELS 9
+#define ZK_MAX_KERNELS 9   // (EmailReveal: the five EmailVerifier roles + zk_substr + zk_app_tail + zk_expand = 8)
 #define ZK_O0_SHORT_ROW 8   // host evaluation of the plan (tests): rows up to this many terms are listed first
 #define ZK_RS_SLOTS 16
 #define ZK_EV_RING 512   // launches whose HIP events are kept for zkwg_timing_summary
@@ -36,6 +36,12 @@ extern "C" int zk_rows_copy_launch(const u8* src, u64 stride, u8* dst, u32 count
 static void rp_free_ring(zkwg_circuit* c);   // the resident pipeline's output ring: chunk-mapped (zkwg_vmm.hip) or plain
 struct zkwg_circuit {
   zkwg_config cfg;
+  zkwg_app_config app{};           // ZKWG_MAIN_EMAIL_REVEAL (zkwg_circuit_create_app)
+  // EmailReveal: zk_substr and zk_app_tail read the record only, so they run on two streams of their own beside EmailVerifier's
+  // roles; the caller's stream waits for both at the end of zkwg_prepare_device (a timed prepare runs them in line instead)
+  hipStream_t app_stream[2] = {nullptr, nullptr};
+  hipEvent_t app_dep = nullptr, app_done[2] = {nullptr, nullptr};
+  u32 pos1_off = 0;                // the Poseidon(1) sparse-round table behind Poseidon(9)'s tables in d_pos
   ZkSched s;
   int device;
   Fr* d_invtab;
@@ -256,13 +262,20 @@ void zk_set_last_error(const char* m) { g_last_error = m; }      // for the C-AB
 
 static int create_impl(const zkwg_config* cfg_in, int device, const char* sym_text, uint64_t sym_len,
                        const char* alias_text, uint64_t alias_len, zkwg_circuit_t** out,
-                       const uint8_t* r1cs = nullptr, uint64_t r1cs_len = 0, const zkwg_regex_source* regex = nullptr) {
+                       const uint8_t* r1cs = nullptr, uint64_t r1cs_len = 0, const zkwg_regex_source* regex = nullptr,
+                       const zkwg_app_config* app = nullptr) {
   if (!cfg_in || !out) return ZKWG_RC_BAD_ARG;
+  if (cfg_in->main_kind == ZKWG_MAIN_EMAIL_REVEAL && !app) {
+    g_last_error = "ZKWG_MAIN_EMAIL_REVEAL takes its parameters from zkwg_app_config: create the handle with zkwg_circuit_create_app";
+    return ZKWG_RC_BAD_CONFIG;
+  }
+  if (app && cfg_in->main_kind != ZKWG_MAIN_EMAIL_REVEAL) { g_last_error = "zkwg_circuit_create_app builds ZKWG_MAIN_EMAIL_REVEAL only"; return ZKWG_RC_BAD_CONFIG; }
   zkwg_config cfg_copy = *cfg_in;
   cfg_copy.layout = ZKWG_LAYOUT_KEPT_V1;
   const zkwg_config* cfg = &cfg_copy;
   zkwg_circuit* c = new zkwg_circuit();
   c->cfg = *cfg;
+  if (app) c->app = *app;
   c->device = -1;
   // tuning knobs
   { const char* v = getenv("ZKWG_RSLB_MERGE_LANES"); c->rs_merge_lanes = v && atoi(v) == 4 ? 4 : 1; }
@@ -305,7 +318,7 @@ static int create_impl(const zkwg_config* cfg_in, int device, const char* sym_te
     fprintf(stderr, "[zkwg] create: %-28s %7.2f s\n", what, std::chrono::duration<double>(now - t_last).count());
     t_last = now;
   };
-  if (!build_sched(*cfg, c->s, c->segs, net)) { g_last_error = "unsupported circuit configuration"; delete c; return ZKWG_RC_BAD_CONFIG; }
+  if (!build_sched(*cfg, c->s, c->segs, net, app)) { g_last_error = "unsupported circuit configuration"; delete c; return ZKWG_RC_BAD_CONFIG; }
   if (c->has_net) {   // how a slot of the template's region is decoded, with host pointers (host expansion, layout-only handles); the device copy follows
     ZkNetDec& D = c->h_netd;
     D.pd = c->net.pd.data(); D.tab = c->net.tabs.data();
@@ -419,6 +432,7 @@ static int create_impl(const zkwg_config* cfg_in, int device, const char* sym_te
     c->kname[k++] = "zk_misc_ev";
     c->kname[k++] = "zk_rsa";
     c->kname[k++] = "zk_poseidon9";
+    if (c->s.app.present) { c->kname[k++] = "zk_substr"; c->kname[k++] = "zk_app_tail"; }
     if (c->s.rslb) { c->kname[k++] = "zk_rslb_chunks"; c->kname[k++] = "zk_rslb_chain"; }
     c->n_kernels = k + 1;
     for (int i = 0; i < k; ++i) c->kslots[i] = 0;
@@ -478,7 +492,7 @@ static int create_impl(const zkwg_config* cfg_in, int device, const char* sym_te
         std::vector<u32>().swap(c->o0_desc); std::vector<u32>().swap(c->o0_src); std::vector<u32>().swap(c->o0_long);
       }
     }
-    if (ok && c->s.main_kind == ZKWG_MAIN_EMAIL_VERIFIER) {
+    if (ok && (c->s.main_kind == ZKWG_MAIN_EMAIL_VERIFIER || c->s.app.present)) {
       std::vector<Fr> C, M, t10;
       build_poseidon_constants(10, 8, 60, C, M);
       ok = zk_build_poseidon_sparse(10, 60, C, M, t10);
@@ -494,6 +508,13 @@ static int create_impl(const zkwg_config* cfg_in, int device, const char* sym_te
         for (u32 i = 0; i < RP * T; ++i) cm.push_back(fr_to_mont(t10[c_part + i]));
         for (u32 i = 0; i < 4 * T; ++i) cm.push_back(fr_to_mont(t10[c_last + i]));
         t10.insert(t10.end(), cm.begin(), cm.end());
+      }
+      if (ok && c->s.app.nullifier) {   // EmailNullifier's outer Poseidon(1): t = 2, R_P = 56
+        std::vector<Fr> C1, M1, t2;
+        build_poseidon_constants(2, 8, 56, C1, M1);
+        ok = zk_build_poseidon_sparse(2, 56, C1, M1, t2);
+        c->pos1_off = (u32)t10.size();
+        t10.insert(t10.end(), t2.begin(), t2.end());
       }
       ok = ok && hipMalloc((void**)&c->d_pos, t10.size() * sizeof(Fr)) == hipSuccess &&
            hipMemcpy(c->d_pos, t10.data(), t10.size() * sizeof(Fr), hipMemcpyHostToDevice) == hipSuccess;
@@ -550,6 +571,13 @@ static int create_impl(const zkwg_config* cfg_in, int device, const char* sym_te
       c->rs_sync = getenv("ZKWG_RSLB_SYNC") ? atoi(getenv("ZKWG_RSLB_SYNC")) : 0;
       c->rs_nside = getenv("ZKWG_RSLB_SIDE_STREAMS") ? std::min(ZK_RS_SLOTS, std::max(1, atoi(getenv("ZKWG_RSLB_SIDE_STREAMS")))) : 4;
     }
+    if (c->s.app.present) {
+      hipEventCreateWithFlags(&c->app_dep, hipEventDisableTiming);
+      for (int i = 0; i < 2; ++i) {
+        hipStreamCreateWithFlags(&c->app_stream[i], hipStreamNonBlocking);
+        hipEventCreateWithFlags(&c->app_done[i], hipEventDisableTiming);
+      }
+    }
     c->pos_lane = getenv("ZKWG_POS_LANE") ? atoi(getenv("ZKWG_POS_LANE")) : 0;
     c->pos_wave_below = getenv("ZKWG_POS_WAVE_BELOW") ? atoi(getenv("ZKWG_POS_WAVE_BELOW")) : 1024;
     for (int i = 0; i < 2; ++i) { hipEventCreateWithFlags(&c->hb_done[i], hipEventDisableTiming); hipEventCreateWithFlags(&c->hb_copied[i], hipEventDisableTiming); }
@@ -565,9 +593,10 @@ static int create_impl(const zkwg_config* cfg_in, int device, const char* sym_te
 // no C++ exception may cross the C ABI (ctypes / N-API callers would abort)
 static int create_guarded(const zkwg_config* cfg, int device, const char* sym_text, uint64_t sym_len,
                           const char* alias_text, uint64_t alias_len, zkwg_circuit_t** out,
-                          const uint8_t* r1cs = nullptr, uint64_t r1cs_len = 0, const zkwg_regex_source* regex = nullptr) {
+                          const uint8_t* r1cs = nullptr, uint64_t r1cs_len = 0, const zkwg_regex_source* regex = nullptr,
+                          const zkwg_app_config* app = nullptr) {
   try {
-    return create_impl(cfg, device, sym_text, sym_len, alias_text, alias_len, out, r1cs, r1cs_len, regex);
+    return create_impl(cfg, device, sym_text, sym_len, alias_text, alias_len, out, r1cs, r1cs_len, regex, app);
   } catch (const std::bad_alloc&) {
     g_last_error = "out of host memory while building the circuit";
     return ZKWG_RC_OOM;
@@ -598,6 +627,10 @@ int zkwg_circuit_create_regex(const zkwg_config* cfg, int device, const zkwg_reg
   if (!regex || !regex->circom_path) return ZKWG_RC_BAD_ARG;
   if (r1cs && !sym_text) return ZKWG_RC_BAD_ARG;
   return create_guarded(cfg, device, sym_text, sym_len, alias_text, alias_len, out, r1cs, r1cs_len, regex);
+}
+int zkwg_circuit_create_app(const zkwg_config* cfg, const zkwg_app_config* app, int device, zkwg_circuit_t** out) {
+  if (!app) return ZKWG_RC_BAD_ARG;
+  return create_guarded(cfg, device, nullptr, 0, nullptr, 0, out, nullptr, 0, nullptr, app);
 }
 int zkwg_regex_info(const zkwg_circuit_t* c, uint64_t out[8]) {
   if (!c || !out) return ZKWG_RC_BAD_ARG;
@@ -703,6 +736,10 @@ void zkwg_circuit_destroy(zkwg_circuit_t* c) {
     for (int i = 0; i < 2; ++i) { hipEventDestroy(c->hb_done[i]); hipEventDestroy(c->hb_copied[i]); if (c->hx_img[i]) hipHostFree(c->hx_img[i]); }
     hipStreamDestroy(c->copy_stream);
     hipStreamDestroy(c->own_stream);
+    if (c->s.app.present) {
+      for (int i = 0; i < 2; ++i) { hipStreamSynchronize(c->app_stream[i]); hipStreamDestroy(c->app_stream[i]); hipEventDestroy(c->app_done[i]); }
+      hipEventDestroy(c->app_dep);
+    }
     if (c->s.rslb) {
       for (int i = 0; i < ZK_RS_SLOTS; ++i) {
         hipStreamSynchronize(c->side_stream[i]);
@@ -750,7 +787,7 @@ int zkwg_pack_input(const zkwg_circuit_t* c, uint8_t* rec, const uint8_t* header
 
 int zkwg_pack_field(const zkwg_circuit_t* c, uint8_t* rec, int field, uint64_t first, const uint8_t* values32,
                     uint64_t count) {
-  if (!c || !rec || !values32 || field < 0 || field >= ZKWG_IN_RANGE_FLAGS) return ZKWG_RC_BAD_ARG;
+  if (!c || !rec || !values32 || field < 0 || field >= ZKWG_IN_NFIELDS || field == ZKWG_IN_RANGE_FLAGS) return ZKWG_RC_BAD_ARG;
   const ZkSched& s = c->s;
   u64 cap = 0;
   u32 width = 1;   // bytes per packed element
@@ -763,6 +800,7 @@ int zkwg_pack_field(const zkwg_circuit_t* c, uint8_t* rec, int field, uint64_t f
     case ZKWG_IN_HEADER_MASK: cap = s.mask_header ? c->cfg.max_header : 0; break;
     case ZKWG_IN_BODY_MASK: cap = s.mask_body ? c->cfg.max_body : 0; break;
     case ZKWG_IN_DECODED_BODY: cap = s.rslb ? c->cfg.max_body : 0; break;
+    case ZKWG_IN_SUBSTRING_START: case ZKWG_IN_SUBSTRING_LEN: cap = s.app.present ? 1 : 0; width = 4; break;
   }
   if (first > cap || count > cap - first) return ZKWG_RC_BAD_ARG;
   u32 flags;
@@ -896,6 +934,7 @@ static void fill_bufs(const zkwg_circuit* c, ZkBufs& B, const void* d_in, u64 n,
   B.rs_list = c->d_rs_zero ? (u32*)(scr + L.off_rs_list) : nullptr;
   B.rs_cnt = c->d_rs_zero ? (u32*)(scr + L.off_rs_list + align256(L.rs_units * 2 * 4)) : nullptr;
   B.pos2 = c->d_pos_rs ? c->d_pos_rs + c->pos2_off : nullptr;
+  B.pos1 = c->pos1_off ? c->d_pos + c->pos1_off : nullptr;
   B.segs = c->d_segs;
   B.wit = nullptr;
   B.wit_stride16 = 0;
@@ -963,7 +1002,21 @@ int zkwg_prepare_device(zkwg_circuit_t* c, const void* d_in, uint64_t n, void* d
   int ki = 0;
   hipEvent_t* evs = c->pev[c->prep_launches % ZK_EV_RING];
   const u32 pm = c->prep_mask;
-  const bool pos9 = s.rsa.present && s.main_kind == ZKWG_MAIN_EMAIL_VERIFIER && (pm & 32u);
+  const bool pos9 = s.rsa.present && (s.main_kind == ZKWG_MAIN_EMAIL_VERIFIER || s.app.present) && (pm & 32u);
+  // EmailReveal: zk_substr (the RevealSubstring component) and zk_app_tail (packed bytes, nullifier) beside the roles below
+  const u32 sub_lds = s.sub.present ? zk_sub_lds_bytes(s.sub.L, s.sub.S) : 0u;
+  auto launch_substr = [&](hipStream_t q) {   // one wavefront per email, in[] and the substring in LDS
+    if (sub_lds > 48u * 1024u) hipFuncSetAttribute((const void*)zk_substr, hipFuncAttributeMaxDynamicSharedMemorySize, (int)sub_lds);
+    hipLaunchKernelGGL(zk_substr, dim3(ne), dim3(64), sub_lds, q, s, B);
+  };
+  const bool app_side = s.app.present && !tm;
+  if (app_side) {
+    hipEventRecord(c->app_dep, st);   // (behind the status memset and whatever wrote the records on this stream)
+    for (int i = 0; i < 2; ++i) hipStreamWaitEvent(c->app_stream[i], c->app_dep, 0);
+    if (pm & 16u) launch_substr(c->app_stream[0]);
+    if (pm & 512u) hipLaunchKernelGGL(zk_app_tail, dim3((ne + 63) / 64), dim3(64), 0, c->app_stream[1], s, B);
+    for (int i = 0; i < 2; ++i) hipEventRecord(c->app_done[i], c->app_stream[i]);
+  }
   if (tm) hipEventRecord(evs[ki], st);
   if (s.nframes && (pm & 1u)) {
     u32 threads = ne * s.nframes;
@@ -1003,17 +1056,22 @@ int zkwg_prepare_device(zkwg_circuit_t* c, const void* d_in, uint64_t n, void* d
     hipLaunchKernelGGL(zk_rsa, dim3(ne), dim3(64), dyn, st, s, B);
   }
   if (s.fpg.present && (pm & 16u)) hipLaunchKernelGGL(zk_fpmul_small, dim3((ne + 63) / 64), dim3(64), 0, st, s, B);   // (timed in zk_rsa's slot)
-  if (s.sub.present && (pm & 16u)) {   // substring mains: one wavefront per email, in[] and the substring in LDS (timed in zk_rsa's slot)
-    const u32 lds = zk_sub_lds_bytes(s.sub.L, s.sub.S);
-    if (lds > 48u * 1024u) hipFuncSetAttribute((const void*)zk_substr, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-    hipLaunchKernelGGL(zk_substr, dim3(ne), dim3(64), lds, st, s, B);
-  }
+  if (s.sub.present && !s.app.present && (pm & 16u)) launch_substr(st);   // substring mains (timed in zk_rsa's slot)
   if (tm) hipEventRecord(evs[++ki], st);
   if (pos9) {
     // one lane per email once the batch supplies >= 16 wavefronts of them; one wavefront per email below
     if ((int)ne < c->pos_wave_below) hipLaunchKernelGGL(zk_poseidon9_wave, dim3(ne), dim3(64), 0, st, s, B);
     else if (c->pos_lane) hipLaunchKernelGGL(zk_poseidon9, dim3((ne + 63) / 64), dim3(64), 0, st, s, B);
     else hipLaunchKernelGGL(zk_poseidon9_g16, dim3((ne + 3) / 4), dim3(64), 0, st, s, B);
+  }
+  if (s.app.present) {
+    if (app_side) for (int i = 0; i < 2; ++i) hipStreamWaitEvent(st, c->app_done[i], 0);
+    else {   // timed: in line, a slot each
+      hipEventRecord(evs[++ki], st);
+      if (pm & 16u) launch_substr(st);
+      hipEventRecord(evs[++ki], st);
+      if (pm & 512u) hipLaunchKernelGGL(zk_app_tail, dim3((ne + 63) / 64), dim3(64), 0, st, s, B);
+    }
   }
   if (s.rslb) {
     // removeSoftLineBreaks: chunk hashes (one lane per 16-byte chunk), then the serial merge chain + scans
@@ -1068,7 +1126,7 @@ static int expand_impl(zkwg_circuit_t* c, const void* d_in, uint64_t n, const vo
   if (count == 0) return ZKWG_RC_OK;
   const ZkSched& s = c->s;
   if (abc && !c->abc_m) return ZKWG_RC_BAD_CONFIG;
-  if (mont && s.sub.present) return ZKWG_RC_BAD_CONFIG;   // substring mains: no Montgomery-form output
+  if (mont && s.sub.present) return ZKWG_RC_BAD_CONFIG;   // substring mains and EmailReveal: no Montgomery-form output
   // the descriptor table written from: the attached system's A.w | B.w | C.w, a numbered circuit's wires, or none (kept-v1 pieces)
   const ZkO0Dev* OD = abc ? &c->abcd : (c->full_W ? &c->o0d : nullptr);
   if (first + count > n || out_stride < (abc ? 3 * c->abc_m : out_W(c)) * 32 || (out_stride & 15)) return ZKWG_RC_BAD_ARG;
@@ -1136,7 +1194,8 @@ static int expand_impl(zkwg_circuit_t* c, const void* d_in, uint64_t n, const vo
       if (units3 > 0x7fffffffull) return ZKWG_RC_BAD_ARG;
       if (mont) hipLaunchKernelGGL(zk_image_to_mont, dim3((u32)((conv + 255) / 256)), dim3(256), 0, st, A);
       const dim3 g3((u32)units3), b3(256);
-      if (s.sub.present) hipLaunchKernelGGL(zk_expand3_subm, g3, b3, 0, st, A);   // (mont was refused above)
+      // (mont was refused above) EmailReveal without the uniqueness check has no match matrix: the plain kernel serves
+      if (s.app.present ? s.sub.uniq != 0 : s.sub.present != 0) hipLaunchKernelGGL(zk_expand3_subm, g3, b3, 0, st, A);
       else hipLaunchKernelGGL(mont ? zk_expand3_mont : zk_expand3, g3, b3, 0, st, A);
     }
   }
@@ -1166,7 +1225,7 @@ int zkwg_circuit_attach_r1cs(zkwg_circuit_t* c, const uint8_t* r1cs, uint64_t le
   std::lock_guard<std::mutex> hb_lock(c->hb_mutex);
   std::lock_guard<std::mutex> lock(c->dev_mutex);
   if (c->abc_m) { g_last_error = "attach_r1cs: the handle already has a constraint system"; return ZKWG_RC_BAD_CONFIG; }
-  if (c->s.sub.present) { g_last_error = "attach_r1cs: not available for the substring mains"; return ZKWG_RC_BAD_CONFIG; }
+  if (c->s.sub.present) { g_last_error = "attach_r1cs: not available for the substring mains and EmailReveal"; return ZKWG_RC_BAD_CONFIG; }
   try {
     ZkR1csHost R;
     if (!zk_r1cs_parse(r1cs, len, R)) { g_last_error = "the .r1cs file could not be parsed: " + R.err; return ZKWG_RC_BAD_CONFIG; }
@@ -1713,7 +1772,7 @@ int zkwg_generate_inputs_device(zkwg_circuit_t* c, const zkwg_dkim_batch* b, uin
                                 void* d_gen_status, void* hip_stream) {
   if (!c || !b || !d_records || !d_gen_status) return ZKWG_RC_BAD_ARG;
   if (c->device < 0) return ZKWG_RC_NO_DEVICE;
-  if (c->s.main_kind != ZKWG_MAIN_EMAIL_VERIFIER) return ZKWG_RC_BAD_CONFIG;
+  if (c->s.main_kind != ZKWG_MAIN_EMAIL_VERIFIER && !c->s.app.present) return ZKWG_RC_BAD_CONFIG;   // (EmailReveal: its two indices are the caller's)
   if (n == 0) return ZKWG_RC_OK;
   if (!b->headers || !b->header_len || !b->pubkey_be || !b->signature_be) return ZKWG_RC_BAD_ARG;
   if (c->s.body && (!b->bodies || !b->body_len || !b->body_hash_b64)) return ZKWG_RC_BAD_ARG;
@@ -1800,6 +1859,7 @@ uint64_t zkwg_write_sym(const zkwg_circuit_t* c, char* out, uint64_t cap) {
     case ZKWG_MAIN_REVEAL_SUBSTRING: zk_walk_main_reveal(w, tmp, tmp.sub.L, tmp.sub.S, tmp.sub.uniq); break;
     case ZKWG_MAIN_COUNT_SUBSTRING: zk_walk_main_count(w, tmp, tmp.sub.L, tmp.sub.S); break;
     case ZKWG_MAIN_EMAIL_VERIFIER: zk_walk_main_ev(w, tmp); break;
+    case ZKWG_MAIN_EMAIL_REVEAL: zk_walk_main_app(w, tmp); break;
   }
   return pos;
 }

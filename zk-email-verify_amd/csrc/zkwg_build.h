@@ -42,9 +42,18 @@ static inline void zk_build_entries(u64 W, const std::vector<ZkSeg>& segs, std::
     } else e.type = ZSEG_NTYPES;
   }
 }
-static bool build_sched(const zkwg_config& cfg, ZkSched& s, std::vector<ZkSeg>& segs, const zkc::Net* net = nullptr) {
+static bool build_sched(const zkwg_config& cfg, ZkSched& s, std::vector<ZkSeg>& segs, const zkc::Net* net = nullptr,
+                        const zkwg_app_config* app = nullptr) {
   memset(&s, 0, sizeof(s));
   if (cfg.layout != ZKWG_LAYOUT_KEPT_V1) return false;
+  if ((cfg.main_kind == ZKWG_MAIN_EMAIL_REVEAL) != (app != nullptr)) return false;
+  if (app) {   // EmailReveal: EmailVerifier's rules for the lengths, no masking / soft-line-break flags, no loaded template
+    if (cfg.remove_soft_line_breaks || cfg.enable_header_masking || cfg.enable_body_masking || net) return false;
+    if (app->reveal_from_body > 1 || app->check_uniqueness > 1 || app->with_nullifier > 1) return false;
+    if (app->reveal_from_body && cfg.ignore_body_hash_check) return false;
+    const u32 L = app->reveal_from_body ? cfg.max_body : cfg.max_header;
+    if (app->max_substring < 2 || app->max_substring >= L || L > 65536) return false;
+  }
   if (cfg.remove_soft_line_breaks && (cfg.main_kind != ZKWG_MAIN_EMAIL_VERIFIER || cfg.ignore_body_hash_check)) return false;
   if ((cfg.enable_header_masking || cfg.enable_body_masking) && cfg.main_kind != ZKWG_MAIN_EMAIL_VERIFIER) return false;
   if (cfg.enable_body_masking && cfg.ignore_body_hash_check) return false;
@@ -75,6 +84,9 @@ static bool build_sched(const zkwg_config& cfg, ZkSched& s, std::vector<ZkSeg>& 
   s.in_off[ZKWG_IN_BODY_MASK] = off; off += cfg.enable_body_masking ? cfg.max_body : 0;
   off = (off + 15u) & ~15u;
   s.in_off[ZKWG_IN_DECODED_BODY] = off; off += cfg.remove_soft_line_breaks ? cfg.max_body : 0;
+  off = (off + 15u) & ~15u;     // (the two fields take room in EmailReveal's records only)
+  s.in_off[ZKWG_IN_SUBSTRING_START] = off; off += app ? 4 : 0;
+  s.in_off[ZKWG_IN_SUBSTRING_LEN] = off; off += app ? 4 : 0;
   s.in_stride = (off + 15u) & ~15u;
   s.rslb = cfg.remove_soft_line_breaks ? 1u : 0u;
   s.mask_header = cfg.enable_header_masking ? 1u : 0u;
@@ -124,6 +136,32 @@ static bool build_sched(const zkwg_config& cfg, ZkSched& s, std::vector<ZkSeg>& 
       if (s.body) max_small = std::max<u64>(max_small, 1ull << s.sel_bits);
       max_small = std::max<u64>(max_small, std::max(s.fr[0].nblocks, s.fr[1].nblocks) + 2);
       break;
+    case ZKWG_MAIN_EMAIL_REVEAL: {
+      if (cfg.n != 121 || cfg.k != 17 || cfg.max_header < 128) return false;
+      s.body = cfg.ignore_body_hash_check ? 0 : 1;
+      if (s.body && cfg.max_body == 0) return false;
+      s.nframes = s.body ? 2 : 1;
+      init_frame(s.fr[0], cfg.max_header, 0, s.in_off[ZKWG_IN_HEADER], s.in_off[ZKWG_IN_HEADER_LEN]);
+      if (s.body) init_frame(s.fr[1], cfg.max_body, 1, s.in_off[ZKWG_IN_BODY], s.in_off[ZKWG_IN_BODY_LEN]);
+      w.sha_rounds = true;
+      ZkAppLayout& A = s.app;
+      A.present = 1; A.from_body = app->reveal_from_body; A.S = app->max_substring;
+      A.chunks = (A.S + ZK_APP_PACK - 1) / ZK_APP_PACK;
+      A.nullifier = app->with_nullifier;
+      A.in_src = s.in_off[A.from_body ? ZKWG_IN_BODY : ZKWG_IN_HEADER];
+      A.src_len = A.from_body ? cfg.max_body : cfg.max_header;
+      A.in_start = s.in_off[ZKWG_IN_SUBSTRING_START]; A.in_len = s.in_off[ZKWG_IN_SUBSTRING_LEN];
+      A.in_sig = s.in_off[ZKWG_IN_SIGNATURE];
+      s.sub.uniq = app->check_uniqueness;
+      zk_walk_main_app(w, s);
+      max_small = std::max<u64>(max_small, 2100);
+      max_small = std::max<u64>(max_small, (u64)cfg.max_header + 64);
+      if (s.body) max_small = std::max<u64>(max_small, 1ull << s.sel_bits);
+      max_small = std::max<u64>(max_small, std::max(s.fr[0].nblocks, s.fr[1].nblocks) + 2);
+      // IsZero(difference[j]): |(in - substring) substring| reaches 255 * 255 (utils/array.circom:211-212)
+      if (s.sub.uniq) max_small = std::max<u64>(max_small, 255 * 255);
+      break;
+    }
     case ZKWG_MAIN_RSA_VERIFIER:
       if (cfg.n != 121 || cfg.k != 17) return false;
       s.nframes = 0;
@@ -217,6 +255,7 @@ static inline void zk_collect_names(ZkSched tmp, std::vector<std::string>& names
     case ZKWG_MAIN_RSA_VERIFIER: zk_walk_main_rsa(w, tmp); break;
     case ZKWG_MAIN_REVEAL_SUBSTRING: zk_walk_main_reveal(w, tmp, tmp.sub.L, tmp.sub.S, tmp.sub.uniq); break;
     case ZKWG_MAIN_COUNT_SUBSTRING: zk_walk_main_count(w, tmp, tmp.sub.L, tmp.sub.S); break;
+    case ZKWG_MAIN_EMAIL_REVEAL: zk_walk_main_app(w, tmp); break;
     default: zk_walk_main_ev(w, tmp); break;
   }
 }

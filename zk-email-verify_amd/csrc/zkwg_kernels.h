@@ -9,6 +9,7 @@ template <bool REC, bool TRACE> __global__ void zk_sha_trace(ZkSched s, ZkBufs B
 __global__ void zk_rsa(ZkSched s, ZkBufs B);         // zkwg_kernels_rsa.hip
 __global__ void zk_fpmul_small(ZkSched s, ZkBufs B);
 __global__ void zk_substr(ZkSched s, ZkBufs B);      // zkwg_kernels_substr.hip
+__global__ void zk_app_tail(ZkSched s, ZkBufs B);    // zkwg_kernels_app.hip
 __global__ void zk_poseidon9(ZkSched s, ZkBufs B);   // zkwg_kernels_rsa.hip
 __global__ void zk_poseidon9_wave(ZkSched s, ZkBufs B);
 __global__ void zk_poseidon9_g16(ZkSched s, ZkBufs B);

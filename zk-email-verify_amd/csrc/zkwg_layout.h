@@ -341,6 +341,17 @@ static inline void zk_sub_record(ZkSubLayout& U, const ZkSched& s, u32 kind, u32
   U.present = kind; U.L = L; U.S = S; U.uniq = uniq;
   U.in_in = s.in_off[0]; U.in_sub = s.in_off[1]; U.in_len = s.in_off[7]; U.in_start = s.in_off[8];
 }
+// the sub-components of RevealSubstring(L, S, uniq) under the path `p`, in creation order: the three range checks,
+// selectSubArray, (uniq) countSubstringOccurrences
+static inline void zk_walk_reveal_subs(ZkWalker& w, const std::string& p, const ZkSubLayout& U) {
+  const u32 L = U.L, S = U.S;
+  const u32 b0 = zk_log2ceil(L) + 1, b1 = zk_log2ceil((u64)S + 1) + 1, b2 = zk_log2ceil((u64)L + 1) + 1;
+  w.seg(ZSEG_BITS, b0, U.b_lt, b0, 1); w.arr(p + ".anon_LessThan_start.n2b.out", b0);
+  w.seg(ZSEG_BITS, b1, U.b_lt + 1, b1, 1); w.arr(p + ".anon_LessThan_length.n2b.out", b1);
+  w.seg(ZSEG_BITS, b2, U.b_lt + 2, b2, 1); w.arr(p + ".anon_LessThan_sum.n2b.out", b2);
+  zk_walk_select_sub_array(w, p + ".selectSubArray", U, U.m_start);
+  if (U.uniq) zk_walk_count_substring(w, p + ".countSubstringOccurrences", U);
+}
 // main = RevealSubstring(L, S, uniq), no public inputs (tests/test-circuits/reveal-substring-test.circom:5;
 // helpers/reveal-substring.circom:13-50).  The three anonymous LessThan call sites (:23, :27, :32) are named
 // anon_LessThan_start / _length / _sum.
@@ -359,12 +370,7 @@ static inline void zk_walk_main_reveal(ZkWalker& w, ZkSched& s, u32 L, u32 S, u3
   w.seg(ZSEG_IN8, L, U.in_in); w.arr("main.in", L);
   w.seg(ZSEG_SMALL, 2, U.m_start);
   w.one("main.substringStartIndex"); w.one("main.substringLength");
-  const u32 b0 = zk_log2ceil(L) + 1, b1 = zk_log2ceil((u64)S + 1) + 1, b2 = zk_log2ceil((u64)L + 1) + 1;
-  w.seg(ZSEG_BITS, b0, U.b_lt, b0, 1); w.arr("main.anon_LessThan_start.n2b.out", b0);
-  w.seg(ZSEG_BITS, b1, U.b_lt + 1, b1, 1); w.arr("main.anon_LessThan_length.n2b.out", b1);
-  w.seg(ZSEG_BITS, b2, U.b_lt + 2, b2, 1); w.arr("main.anon_LessThan_sum.n2b.out", b2);
-  zk_walk_select_sub_array(w, "main.selectSubArray", U, U.m_start);
-  if (uniq) zk_walk_count_substring(w, "main.countSubstringOccurrences", U);
+  zk_walk_reveal_subs(w, "main", U);
   s.n_public = S;   // outputs only
 }
 // main = CountSubstringOccurrences(L, S), no public inputs (tests/test-circuits/count-substring-occurrences-test.circom:5)
@@ -575,10 +581,11 @@ static inline void zk_walk_azp(ZkWalker& w, const std::string& p, const ZkShaFra
   if (!w.names) w.skip((u64)f.max_bytes * (bl + 1));
   else for (u32 i = 0; i < f.max_bytes; ++i) w.arr(zk_idx(p + ".lessThans", i) + ".n2b.out", bl + 1);
 }
-static inline void zk_walk_main_ev(ZkWalker& w, ZkSched& s) {
+// The main is walked in three parts so that EmailReveal (below) can compose it: image allocations, main I/O, and the
+// sub-components under a path prefix `p` ("main" for the plain main, "main.ev" inside EmailReveal).
+static inline void zk_alloc_ev(ZkWalker& w, ZkSched& s) {
   const u32 N = s.fr[0].max_bytes;
   const u32 M = s.body ? s.fr[1].max_bytes : 0;
-  // image allocations
   s.m_one = w.alloc_small(1);
   s.f_out = w.alloc_fr(3);
   zk_frame_len_alloc(w, s.fr[0]);
@@ -599,8 +606,11 @@ static inline void zk_walk_main_ev(ZkWalker& w, ZkSched& s) {
     if (s.rslb) zk_alloc_rslb(w, s, M);
   }
   s.f_pos = w.alloc_fr(420);
-
-  // main I/O: [1], outputs, public inputs, private inputs
+}
+// main I/O: [1], outputs, public inputs, private inputs
+static inline void zk_walk_ev_io(ZkWalker& w, ZkSched& s) {
+  const u32 N = s.fr[0].max_bytes;
+  const u32 M = s.body ? s.fr[1].max_bytes : 0;
   w.seg(ZSEG_SMALL, 1, s.m_one); w.one("one");
   w.seg(ZSEG_FR, 3, s.f_out);
   w.one("main.pubkeyHash"); w.one("main.shaHi"); w.one("main.shaLo");
@@ -619,25 +629,34 @@ static inline void zk_walk_main_ev(ZkWalker& w, ZkSched& s) {
     if (s.rslb) { w.seg(ZSEG_IN8, M, s.in_off[11]); w.arr("main.decodedEmailBodyIn", M); }
     if (s.mask_body) { w.seg(ZSEG_IN8, M, s.in_off[10]); w.arr("main.bodyMask", M); }
   }
-  // sub-components in creation order
+}
+// PoseidonLarge(121,17) -> Poseidon(9): 8x10 + 60 S-boxes x (out, in2, in4); `p` = the PoseidonLarge component
+static inline void zk_walk_poseidon_large(ZkWalker& w, const std::string& p, u32 f_pos) {
+  w.seg(ZSEG_FR, 420, f_pos);
+  zk_walk_poseidon_names(w, p + ".anon_Poseidon", 10, 60);
+}
+// sub-components in creation order
+static inline void zk_walk_ev_subs(ZkWalker& w, const std::string& p, ZkSched& s) {
+  const u32 N = s.fr[0].max_bytes;
+  const u32 M = s.body ? s.fr[1].max_bytes : 0;
   const u32 blh = zk_log2ceil(N);
   w.seg(ZSEG_BITS, blh, s.fr[0].b_len, blh, 1);
-  w.arr("main.n2bHeaderLength.out", blh);
-  zk_walk_azp(w, "main.anon_AssertZeroPadding_header", s.fr[0]);
-  zk_walk_sha_frame(w, "main.anon_Sha256Bytes", s.fr[0]);
-  zk_walk_rsa(w, "main.rsaVerifier", s.rsa);
+  w.arr(p + ".n2bHeaderLength.out", blh);
+  zk_walk_azp(w, p + ".anon_AssertZeroPadding_header", s.fr[0]);
+  zk_walk_sha_frame(w, p + ".anon_Sha256Bytes", s.fr[0]);
+  zk_walk_rsa(w, p + ".rsaVerifier", s.rsa);
   if (s.mask_header) {  // ByteMask(maxHeadersLength) (utils/bytes.circom:173-185): out[i] <== in[i] * mask[i]
     w.seg(ZSEG_IN8MASK, N, s.fr[0].in_data, s.in_off[9]);
-    w.arr("main.byteMask_header.out", N);
+    w.arr(p + ".byteMask_header.out", N);
   }
   if (s.body) {
     const u32 blb = zk_log2ceil(M);
     w.seg(ZSEG_BITS, blb, s.fr[1].b_len, blb, 1);
-    w.arr("main.n2bBodyLength.out", blb);
-    zk_walk_azp(w, "main.anon_AssertZeroPadding_body", s.fr[1]);
-    zk_walk_bh_regex(w, "main.anon_BodyHashRegex", s, N);
+    w.arr(p + ".n2bBodyLength.out", blb);
+    zk_walk_azp(w, p + ".anon_AssertZeroPadding_body", s.fr[1]);
+    zk_walk_bh_regex(w, p + ".anon_BodyHashRegex", s, N);
     // SelectRegexReveal(N, 44) (utils/regex.circom:17-52)
-    const std::string sr = "main.anon_SelectRegexReveal";
+    const std::string sr = p + ".anon_SelectRegexReveal";
     const u32 bl = s.sel_bits, per = 6 + bl + 1;
     w.seg(ZSEG_REGSEL, (u64)(per - 2) + (u64)(N - 1) * per, s.m_bh_idx, bl, s.m_rev, N);
     if (!w.names) w.skip((u64)(per - 2) + (u64)(N - 1) * per);
@@ -652,7 +671,7 @@ static inline void zk_walk_main_ev(ZkWalker& w, ZkSched& s) {
     w.seg(ZSEG_BITS, blh, s.b_shift, blh, 1);
     w.arr(sr + ".anon_VarShiftLeft.n2b.out", blh);
     // Base64Decode(32) (lib/base64.circom:14-64)
-    const std::string b64 = "main.anon_Base64Decode";
+    const std::string b64 = p + ".anon_Base64Decode";
     w.seg(ZSEG_B64BITS, 44 * 6, s.m_chars);
     for (u32 g = 0; g < 11; ++g) for (u32 j = 0; j < 4; ++j)
       w.arr(b64 + ".bitsIn[" + std::to_string(g) + "][" + std::to_string(j) + "].out", 6);
@@ -666,23 +685,70 @@ static inline void zk_walk_main_ev(ZkWalker& w, ZkSched& s) {
       const char* eqs[3] = {"equal_plus", "equal_slash", "equal_eqsign"};
       for (auto m : eqs) { w.one(t + "." + m + ".out"); w.one(t + "." + m + ".inv"); }
     }
-    zk_walk_sha_frame(w, "main.anon_Sha256BytesPartial", s.fr[1]);
-    if (s.rslb) zk_walk_rslb(w, "main.qpEncodingChecker", s, M);
+    zk_walk_sha_frame(w, p + ".anon_Sha256BytesPartial", s.fr[1]);
+    if (s.rslb) zk_walk_rslb(w, p + ".qpEncodingChecker", s, M);
     if (s.mask_body) {
       w.seg(ZSEG_IN8MASK, M, s.fr[1].in_data, s.in_off[10]);
-      w.arr("main.byteMask_body.out", M);
+      w.arr(p + ".byteMask_body.out", M);
     }
   }
-  // PoseidonLarge(121,17) -> Poseidon(9): 8x10 + 60 S-boxes x (out, in2, in4)
-  w.seg(ZSEG_FR, 420, s.f_pos);
-  const std::string pp = "main.anon_PoseidonLarge.anon_Poseidon.pEx";
-  for (u32 r = 0; r < 8; ++r) for (u32 j = 0; j < 10; ++j) {
-    std::string t = pp + ".sigmaF[" + std::to_string(r) + "][" + std::to_string(j) + "]";
-    w.one(t + ".out"); w.one(t + ".in2"); w.one(t + ".in4");
-  }
-  for (u32 r = 0; r < 60; ++r) {
-    std::string t = zk_idx(pp + ".sigmaP", r);
-    w.one(t + ".out"); w.one(t + ".in2"); w.one(t + ".in4");
-  }
+  zk_walk_poseidon_large(w, p + ".anon_PoseidonLarge", s.f_pos);
+}
+static inline void zk_walk_main_ev(ZkWalker& w, ZkSched& s) {
+  const u32 N = s.fr[0].max_bytes;
+  const u32 M = s.body ? s.fr[1].max_bytes : 0;
+  zk_alloc_ev(w, s);
+  zk_walk_ev_io(w, s);
+  zk_walk_ev_subs(w, "main", s);
   s.n_public = 3 + (s.mask_header ? N : 0) + (s.mask_body ? M : 0) + 17;
+}
+
+// ------------------------------------------------------------------ EmailReveal main (circuits/email-reveal.circom)
+// EmailReveal(maxHeadersLength, maxBodyLength, n, k, ignoreBodyHashCheck, revealFromBody, maxSubstringLength,
+// shouldCheckUniqueness, withNullifier), no public inputs: ev = EmailVerifier(..., 0, 0, 0), rs = RevealSubstring over the
+// header or the body, revealed = PackBytes(rs.substring), emailNullifier = EmailNullifier(n, k)(signature).  Kept: the
+// constant, the outputs, the inputs, ev's sub-components, rs's, the nullifier's S-boxes.  ev.pubkeyHash / shaHi / shaLo,
+// rs.substring, signatureHash, PackBytes' intSums and every sub-component copy of an input are linear: dropped.
+static inline void zk_walk_main_app(ZkWalker& w, ZkSched& s) {
+  ZkAppLayout& A = s.app;
+  ZkSubLayout& U = s.sub;
+  const u32 N = s.fr[0].max_bytes;
+  const u32 M = s.body ? s.fr[1].max_bytes : 0;
+  zk_alloc_ev(w, s);
+  U.present = 1; U.L = A.src_len; U.S = A.S;
+  U.in_in = A.in_src; U.in_sub = 0; U.in_len = A.in_len; U.in_start = A.in_start;
+  U.m_sub = w.alloc_small(U.S);
+  if (U.uniq) w.alloc_small(U.L);               // the leading-match lengths follow the substring (ZSEG_SUBM)
+  U.m_start = w.alloc_small(2);
+  U.b_lt = w.alloc_bits(3);
+  zk_alloc_select_sub_array(w, U);
+  A.f_out = w.alloc_fr(A.nullifier + A.chunks);
+  A.f_pos = A.nullifier ? w.alloc_fr(ZK_P9_KEPT + ZK_P1_KEPT) : 0;
+  // main I/O: the constant, the outputs, the inputs in declaration order
+  w.seg(ZSEG_SMALL, 1, s.m_one); w.one("one");
+  w.seg(ZSEG_FR, 1, s.f_out); w.one("main.pubkeyHash");
+  w.seg(ZSEG_FR, A.nullifier + A.chunks, A.f_out);
+  if (A.nullifier) w.one("main.emailNullifier");
+  w.arr("main.revealed", A.chunks);
+  w.seg(ZSEG_IN8, N, s.fr[0].in_data); w.arr("main.emailHeader", N);
+  w.seg(ZSEG_SMALL, 1, s.fr[0].m_len); w.one("main.emailHeaderLength");
+  w.seg(ZSEG_LIMB, 17, s.rsa.in_mod); w.arr("main.pubkey", 17);
+  w.seg(ZSEG_LIMB, 17, s.rsa.in_sig); w.arr("main.signature", 17);
+  if (s.body) {
+    w.seg(ZSEG_SMALL, 1, s.m_bh_idx); w.one("main.bodyHashIndex");
+    w.seg(ZSEG_IN8, 32, s.fr[1].in_pre); w.arr("main.precomputedSHA", 32);
+    w.seg(ZSEG_IN8, M, s.fr[1].in_data); w.arr("main.emailBody", M);
+    w.seg(ZSEG_SMALL, 1, s.fr[1].m_len); w.one("main.emailBodyLength");
+  }
+  w.seg(ZSEG_SMALL, 2, U.m_start);
+  w.one("main.substringStartIndex"); w.one("main.substringLength");
+  zk_walk_ev_subs(w, "main.ev", s);
+  zk_walk_reveal_subs(w, "main.rs", U);
+  if (A.nullifier) {
+    const std::string en = "main.anon_EmailNullifier";
+    zk_walk_poseidon_large(w, en + ".anon_PoseidonLarge", A.f_pos);
+    w.seg(ZSEG_FR, ZK_P1_KEPT, A.f_pos + ZK_P9_KEPT);
+    zk_walk_poseidon_names(w, en + ".anon_Poseidon", 2, 56);
+  }
+  s.n_public = 1 + A.nullifier + A.chunks;   // outputs only
 }

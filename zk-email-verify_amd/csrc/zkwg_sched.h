@@ -201,6 +201,22 @@ struct ZkSubLayout {
   u32 b_shift;           // bits: 1 word, substringStartIndex (VarShiftLeft.n2b)
   u32 b_gts;             // bits: S words, the Num2Bits inputs of gts[i] = GreaterThan(log2Ceil(S))(length, i)
 };
+// main = EmailReveal(...) (circuits/email-reveal.circom; zkwg_app_core.h): what zk_app_tail writes beside EmailVerifier's and
+// RevealSubstring's (ZkSched::sub) values
+struct ZkAppLayout {
+  u32 present;           // 1: main = EmailReveal
+  u32 from_body;         // RevealSubstring runs over emailBody (else emailHeader)
+  u32 S, chunks;         // maxSubstringLength, computeIntChunkLength(S) = ceil(S / 31)
+  u32 nullifier;         // 1: emailNullifier and its two Poseidon instances are part of the circuit
+  u32 in_src, src_len;   // record offset and maximum length of the revealed-from bytes
+  u32 in_start, in_len;  // record offsets of substringStartIndex, substringLength (u32)
+  u32 in_sig;            // record offset of the signature limbs
+  u32 f_out;             // fr: (nullifier) emailNullifier, then revealed[chunks]
+  u32 f_pos;             // fr: (nullifier) 420 S-box signals of Poseidon(9), then 216 of Poseidon(1)
+};
+#define ZK_APP_PACK 31u       // MAX_BYTES_IN_FIELD (utils/constants.circom)
+#define ZK_P9_KEPT 420u       // Poseidon(9):  3 * (8 * 10 + 60)
+#define ZK_P1_KEPT 216u       // Poseidon(1):  3 * (8 * 2 + 56)
 // bytes of zk_substr's working set (LDS): in[] | substring[] | 64 partial counts + the failure flag
 ZK_HD u32 zk_sub_lds_bytes(u32 L, u32 S) { return ((L + 15u) & ~15u) + ((S + 15u) & ~15u) + 65u * 4u; }
 // RSAVerifier65537(121,17) (lib/rsa.circom:13-46)
@@ -227,7 +243,7 @@ struct ZkSched {
   u32 total_blocks;      // sum of nblocks
   u32 hstates_per_email; // sum of (nblocks+1)
   u32 in_stride;         // bytes per input record
-  u32 in_off[13];        // enum zkwg_input_field -> byte offset (12 = ZK_IN_RANGE_FLAGS)
+  u32 in_off[15];        // enum zkwg_input_field -> byte offset (12 = ZK_IN_RANGE_FLAGS; 13, 14: EmailReveal's start index and length)
   u32 n_public;
   u32 nsegs;
   u32 img_bits;          // u64 words per email
@@ -241,7 +257,8 @@ struct ZkSched {
   u32 m_hdr_len;         // small: emailHeaderLength / paddedInLength
   ZkRsaLayout rsa;
   ZkFpgLayout fpg;       // main = FpMul(n, k) with small parameters
-  ZkSubLayout sub;       // main = RevealSubstring / CountSubstringOccurrences
+  ZkSubLayout sub;       // main = RevealSubstring / CountSubstringOccurrences; EmailReveal: its RevealSubstring component
+  ZkAppLayout app;       // main = EmailReveal
   // EmailVerifier main (email-verifier.circom:42-174)
   u32 f_out;             // fr: pubkeyHash, shaHi, shaLo
   u32 f_pos;             // fr: 420 Poseidon S-box signals
@@ -322,6 +339,7 @@ struct ZkBufs {
   const Fr* pos_m;       // Poseidon(9) dense tables for the wave-collective small-batch kernel: C[680], M[100] (Montgomery)
   const Fr* pos16;       // Poseidon(16) sparse-round table (zkwg_poseidon_sparse.h), removeSoftLineBreaks only
   const Fr* pos2;        // Poseidon(2)  sparse-round table
+  const Fr* pos1;        // Poseidon(1)  sparse-round table (t = 2, R_P = 56), EmailReveal's nullifier only
   const u32* pos16_l29;  // Poseidon(16) table in 29-bit limb form (zkwg_poseidon29.h): what zk_rslb_chunks reads
   const u32* pos2_l29;   // Poseidon(2) table in the same form: zk_rslb_merge1
   u32 rs_prio;           // zk_rslb_merge1 raises its wavefronts' issue priority (ZKWG_RSLB_MERGE_PRIO=0: off)

@@ -20,7 +20,9 @@ const BASE_FIELD_MODULUS = 21888242871839275222246405745257275088696311157297823
 const MAIN_EMAIL_VERIFIER = 0, MAIN_SHA256_BYTES = 1, MAIN_RSA_VERIFIER = 2, MAIN_FP_MUL = 3;
 // RevealSubstring(maxHeader, maxBody, n) / CountSubstringOccurrences(maxHeader, maxBody): helpers/reveal-substring.circom, utils/array.circom:226-254
 const MAIN_REVEAL_SUBSTRING = 4, MAIN_COUNT_SUBSTRING = 5;
-const IN = { HEADER: 0, BODY: 1, PRECOMPUTED_SHA: 2, PUBKEY: 3, SIGNATURE: 4, MESSAGE: 5, HEADER_LEN: 6, BODY_LEN: 7, BODY_HASH_INDEX: 8, HEADER_MASK: 9, BODY_MASK: 10, DECODED_BODY: 11, RANGE_FLAGS: 12 };
+// EmailReveal(maxHeader, maxBody, n, k, ignoreBodyHashCheck, revealFromBody, maxSubstring, checkUniqueness, withNullifier): circuits/email-reveal.circom
+const MAIN_EMAIL_REVEAL = 6;
+const IN = { HEADER: 0, BODY: 1, PRECOMPUTED_SHA: 2, PUBKEY: 3, SIGNATURE: 4, MESSAGE: 5, HEADER_LEN: 6, BODY_LEN: 7, BODY_HASH_INDEX: 8, HEADER_MASK: 9, BODY_MASK: 10, DECODED_BODY: 11, RANGE_FLAGS: 12, SUBSTRING_START: 13, SUBSTRING_LEN: 14 };
 
 function norm(v) {
   let x = BigInt(v) % FIELD_MODULUS;
@@ -33,7 +35,9 @@ class Circuit {
    *  sym: text of the compiled circuit's `.sym` file -> the witness follows its indices (zkwg_circuit_create_sym);
    *  r1cs: Buffer with its `.r1cs` -> complete witness of an --O0 / --O1 build (zkwg_circuit_create_full); device < 0 = layout-only handle;
    *  regex (+ regexIncludeDirs, regexTemplate): path of a zk-regex style `body_hash_regex.circom` -> BodyHashRegex is compiled
-   *  from the template text instead of zkwg's built-in circuit (zkwg_circuit_create_regex) */
+   *  from the template text instead of zkwg's built-in circuit (zkwg_circuit_create_regex);
+   *  mainKind MAIN_EMAIL_REVEAL: + revealFromBody, maxSubstring, checkUniqueness (default 1), withNullifier (default 1) -> EmailVerifier with
+   *  RevealSubstring, the revealed bytes packed 31 per public signal, and the email nullifier (zkwg_circuit_create_app) */
   constructor(opts, device) {
     this.opts = Object.assign({ mainKind: MAIN_EMAIL_VERIFIER, maxHeader: 1024, maxBody: 1536, n: 121, k: 17, ignoreBodyHashCheck: 0, enableHeaderMasking: 0, enableBodyMasking: 0, removeSoftLineBreaks: 0 }, opts || {});
     this.device = device === undefined ? 0 : device;
@@ -76,6 +80,7 @@ class Circuit {
       if (o.removeSoftLineBreaks) s.decodedEmailBodyIn = o.maxBody;
       if (o.enableBodyMasking) s.bodyMask = o.maxBody;
     }
+    if (o.mainKind === MAIN_EMAIL_REVEAL) Object.assign(s, { substringStartIndex: 1, substringLength: 1 });
     return s;
   }
 
@@ -146,6 +151,9 @@ class Circuit {
       if (!o.ignoreBodyHashCheck) {
         bytes(IN.BODY, flat.emailBody, 'emailBody'); u32(IN.BODY_LEN, flat.emailBodyLength[0], 'emailBodyLength');
         bytes(IN.PRECOMPUTED_SHA, flat.precomputedSHA, 'precomputedSHA'); u32(IN.BODY_HASH_INDEX, flat.bodyHashIndex[0], 'bodyHashIndex');
+      }
+      if (o.mainKind === MAIN_EMAIL_REVEAL) {   // record fields of their own: 7 and 8 hold EmailVerifier's
+        u32(IN.SUBSTRING_START, flat.substringStartIndex[0], 'substringStartIndex'); u32(IN.SUBSTRING_LEN, flat.substringLength[0], 'substringLength');
       }
     }
     return rec;
@@ -420,4 +428,4 @@ function symbols(circuit) {
 }
 
 module.exports = { symbols, R1cs, Circuit, WitnessCalculator, MultiCalculator, Prover, Tester, tester, wtns, groth16, FIELD_MODULUS, MAIN_EMAIL_VERIFIER, MAIN_SHA256_BYTES, MAIN_RSA_VERIFIER, MAIN_FP_MUL,
-  MAIN_REVEAL_SUBSTRING, MAIN_COUNT_SUBSTRING };
+  MAIN_REVEAL_SUBSTRING, MAIN_COUNT_SUBSTRING, MAIN_EMAIL_REVEAL };

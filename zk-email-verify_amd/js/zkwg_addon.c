@@ -75,7 +75,20 @@ static napi_value CreateCircuit(napi_env env, napi_callback_info info) {
   get_str(env, argv[0], "regexIncludeDirs", &rdirs, &rdirs_len);
   get_str(env, argv[0], "regexTemplate", &rtmpl, &rtmpl_len);
   int rc;
-  if (regex) {
+  if (cfg.main_kind == ZKWG_MAIN_EMAIL_REVEAL) {
+    /* the application main: `revealFromBody`, `maxSubstring`, `checkUniqueness`, `withNullifier` (zkwg_circuit_create_app) */
+    zkwg_app_config app; memset(&app, 0, sizeof(app));
+    get_u32(env, argv[0], "revealFromBody", &app.reveal_from_body, 0);
+    get_u32(env, argv[0], "maxSubstring", &app.max_substring, 0);
+    get_u32(env, argv[0], "checkUniqueness", &app.check_uniqueness, 1);
+    get_u32(env, argv[0], "withNullifier", &app.with_nullifier, 1);
+    if (sym || r1cs || regex) {
+      free(sym); free(alias); free(regex); free(rdirs); free(rtmpl);
+      napi_throw_error(env, NULL, "zkwg: unsupported circuit configuration: EmailReveal has no .sym / numbered layout and takes no regex template");
+      return NULL;
+    }
+    rc = zkwg_circuit_create_app(&cfg, &app, device, &c);
+  } else if (regex) {
     zkwg_regex_source src = {regex, rdirs, rtmpl};
     rc = zkwg_circuit_create_regex(&cfg, device, &src, sym, sym_len, alias, alias_len, (const uint8_t*)r1cs, r1cs_len, &c);
   } else

@@ -15,7 +15,7 @@ import ctypes as C
 
 from . import _lib
 from ._lib import (Config, MAIN_EMAIL_VERIFIER, MAIN_SHA256_BYTES, MAIN_RSA_VERIFIER, MAIN_FP_MUL, MAIN_REVEAL_SUBSTRING,
-                   MAIN_COUNT_SUBSTRING)
+                   MAIN_COUNT_SUBSTRING, MAIN_EMAIL_REVEAL)
 
 FIELD_MODULUS = 21888242871839275222246405745257275088548364400416034343698204186575808495617
 
@@ -51,6 +51,8 @@ _FIELD_OF = {"emailHeader": 0, "paddedIn": 0, "emailBody": 1, "precomputedSHA": 
              "bodyHashIndex": 8, "headerMask": 9, "bodyMask": 10, "decodedEmailBodyIn": 11,
              # RevealSubstring / CountSubstringOccurrences (helpers/reveal-substring.circom:16-18, utils/array.circom:229-230)
              "in": 0, "substring": 1, "substringLength": 7, "substringStartIndex": 8}
+# EmailReveal (circuits/email-reveal.circom): the two indices have record fields of their own (7 and 8 hold EmailVerifier's)
+_FIELD_OF_APP = dict(_FIELD_OF, substringStartIndex=13, substringLength=14)
 
 
 class Circuit:
@@ -59,8 +61,11 @@ class Circuit:
     def __init__(self, main_kind=MAIN_EMAIL_VERIFIER, max_header=1024, max_body=1536, n=121, k=17,
                  ignore_body_hash_check=0, device=0, enable_header_masking=0, enable_body_masking=0,
                  remove_soft_line_breaks=0, sym=None, sym_alias=None, r1cs=None, regex=None, regex_include_dirs=(),
-                 regex_template=None):
-        """regex: path of a zk-regex style template (`body_hash_regex.circom`): BodyHashRegex is compiled from that
+                 regex_template=None, reveal_from_body=0, max_substring=0, check_uniqueness=1, with_nullifier=1):
+        """main_kind = MAIN_EMAIL_REVEAL: EmailVerifier(max_header, max_body, n, k, ignore_body_hash_check, 0, 0, 0) with
+        RevealSubstring(max_substring, check_uniqueness) over the header (reveal_from_body = 0) or the body, the revealed bytes
+        packed 31 per public signal, and (with_nullifier) the email nullifier (zkwg_circuit_create_app).
+        regex: path of a zk-regex style template (`body_hash_regex.circom`): BodyHashRegex is compiled from that
         file instead of zkwg's built-in DFA circuit (zkwg_circuit_create_regex; regex_include_dirs: where its
         includes are searched; regex_template: template name, default BodyHashRegex).
         sym: text of the compiled circuit's `.sym` file -> the witness follows ITS indices
@@ -72,7 +77,13 @@ class Circuit:
         self.cfg = Config(main_kind, max_header, max_body, n, k, ignore_body_hash_check, enable_header_masking,
                           enable_body_masking, remove_soft_line_breaks, 0)
         h = C.c_void_p()
-        if regex is not None:
+        self.app = None
+        if main_kind == MAIN_EMAIL_REVEAL:
+            if sym is not None or r1cs is not None or regex is not None:
+                raise ZkwgError("EmailReveal has no .sym / numbered layout and takes no regex template")
+            self.app = _lib.AppConfig(reveal_from_body, max_substring, check_uniqueness, with_nullifier)
+            rc = self.lib.zkwg_circuit_create_app(C.byref(self.cfg), C.byref(self.app), device, C.byref(h))
+        elif regex is not None:
             src = _lib.RegexSource(str(regex).encode(), ":".join(str(d) for d in regex_include_dirs).encode(),
                                    regex_template.encode() if regex_template else None)
             sb = None if sym is None else (sym.encode() if isinstance(sym, str) else bytes(sym))
@@ -143,6 +154,8 @@ class Circuit:
                 sizes["decodedEmailBodyIn"] = c.max_body
             if c.enable_body_masking:
                 sizes["bodyMask"] = c.max_body
+        if c.main_kind == MAIN_EMAIL_REVEAL:
+            sizes.update({"substringStartIndex": 1, "substringLength": 1})
         return sizes
 
     def pack(self, inp):
@@ -167,22 +180,23 @@ class Circuit:
         # range flag and the circuit's own range check of that signal fails the email ("Assert Failed"),
         # as circom_runtime does for the same input.
         generic = []
+        field_of = _FIELD_OF_APP if self.cfg.main_kind == MAIN_EMAIL_REVEAL else _FIELD_OF
 
         def as_bytes(vals, what):
             if any(v > 255 for v in vals):
-                generic.append((_FIELD_OF[what], vals))
+                generic.append((field_of[what], vals))
                 return bytes(v & 0xFF for v in vals)
             return bytes(vals)
 
         def as_u32(v, what):
             if v >> 32:
-                generic.append((_FIELD_OF[what], [v]))
+                generic.append((field_of[what], [v]))
                 return v & 0xFFFFFFFF
             return v
 
         def as_limbs(vals, what):
             if any(v >> 128 for v in vals):
-                generic.append((_FIELD_OF[what], vals))
+                generic.append((field_of[what], vals))
             return _limbs_bytes([v & ((1 << 128) - 1) for v in vals] + [0] * (17 - len(vals)))
 
         c = self.cfg
@@ -225,6 +239,9 @@ class Circuit:
             _check(self.lib.zkwg_pack_masks(self.h, rec, hm, bm))
         if c.main_kind == MAIN_EMAIL_VERIFIER and c.remove_soft_line_breaks:
             _check(self.lib.zkwg_pack_decoded_body(self.h, rec, as_bytes(flat["decodedEmailBodyIn"], "decodedEmailBodyIn")))
+        if c.main_kind == MAIN_EMAIL_REVEAL:
+            for key, field in (("substringStartIndex", _lib.IN_SUBSTRING_START), ("substringLength", _lib.IN_SUBSTRING_LEN)):
+                C.c_uint32.from_buffer(rec, self.lib.zkwg_input_offset(self.h, field)).value = as_u32(flat[key][0], key)
         for field, vals in generic:
             buf = b"".join(int(v).to_bytes(32, "little") for v in vals)
             _check(self.lib.zkwg_pack_field(self.h, rec, field, 0, buf, len(vals)))
@@ -755,6 +772,10 @@ class WitnessCalculator:
             elif cfg.main_kind == MAIN_COUNT_SUBSTRING:
                 data = zr.write_r1cs(len(sym), zr.count_substring_main_constraints(sym, cfg.max_header, cfg.max_body),
                                      1, 0, cfg.max_header + cfg.max_body)
+            elif cfg.main_kind == MAIN_EMAIL_REVEAL:
+                a = c.app
+                data = zr.email_reveal_r1cs(sym, cfg.max_header, cfg.max_body, cfg.ignore_body_hash_check, a.reveal_from_body,
+                                            a.max_substring, a.check_uniqueness, a.with_nullifier)
             else:
                 data = zr.email_verifier_r1cs(sym, cfg.max_header, cfg.max_body, cfg.enable_header_masking,
                                               cfg.enable_body_masking, cfg.remove_soft_line_breaks, cfg.ignore_body_hash_check)
@@ -771,8 +792,9 @@ def witness_ints(b):
     return [int.from_bytes(b[i:i + 32], "little") for i in range(0, len(b), 32)]
 
 
-def generate_inputs_device(circuit, dkim_results, selector=None, stream=None):
-    """Batched input generation on the GPU (zkwg_generate_inputs_device).  dkim_results: list of dicts with
+def generate_inputs_device(circuit, dkim_results, selector=None, stream=None, substrings=None):
+    """Batched input generation on the GPU (zkwg_generate_inputs_device).  EmailReveal: substrings = [(start, length), ...],
+    one pair per email, written into the device records' two index fields with a strided copy.  dkim_results: list of dicts with
     headers, body, bodyHash, publicKey, signature (as `verifyDKIMSignature` returns them), or the handle of
     zkwg.dkim.verify_batch_device, whose batch is on the device already.  Returns
     (records: torch.uint8[n, in_stride] on the device, gen_status: list[int])."""
@@ -810,6 +832,18 @@ def generate_inputs_device(circuit, dkim_results, selector=None, stream=None):
     recs = torch.empty((n, circuit.in_stride), dtype=torch.uint8, device=dev)
     st = torch.zeros(n, dtype=torch.int32, device=dev)
     sp = stream.cuda_stream if stream is not None else 0
+    if (circuit.cfg.main_kind == MAIN_EMAIL_REVEAL) != (substrings is not None):
+        raise ZkwgError("substrings=[(start, length), ...] goes with an EmailReveal circuit, and only with one")
+    if substrings is not None and len(substrings) != n:
+        raise ZkwgError("substrings needs one (start, length) pair per email")
     _check(circuit.lib.zkwg_generate_inputs_device(circuit.h, C.byref(b), n, recs.data_ptr(), st.data_ptr(), sp))
+    if substrings is not None:     # after the kernel (it clears the records): the two u32 fields lie side by side
+        off = circuit.lib.zkwg_input_offset(circuit.h, _lib.IN_SUBSTRING_START)
+        assert circuit.lib.zkwg_input_offset(circuit.h, _lib.IN_SUBSTRING_LEN) == off + 4
+        raw = torch.frombuffer(bytearray(b"".join(int(a).to_bytes(4, "little") + int(l).to_bytes(4, "little") for a, l in substrings)),
+                               dtype=torch.uint8).reshape(n, 8)
+        import contextlib
+        with torch.cuda.stream(stream) if stream is not None else contextlib.nullcontext():
+            recs[:, off:off + 8].copy_(raw.to(dev))
     torch.cuda.synchronize()
     return recs, st.cpu().tolist()

@@ -29,6 +29,11 @@ class Config(C.Structure):
     ]
 
 
+class AppConfig(C.Structure):   # zkwg_app_config
+    _fields_ = [("reveal_from_body", C.c_uint32), ("max_substring", C.c_uint32), ("check_uniqueness", C.c_uint32),
+                ("with_nullifier", C.c_uint32)]
+
+
 class SetupSlices(C.Structure):   # zkwg_setup_slices
     _fields_ = [("power", C.c_uint32), ("on_device", C.c_uint32), ("tau_g1", C.c_void_p), ("tau_g2", C.c_void_p), ("alpha_tau_g1", C.c_void_p),
                 ("beta_tau_g1", C.c_void_p), ("tau_g1_next", C.c_void_p), ("alpha1", C.c_uint8 * 64), ("beta1", C.c_uint8 * 64), ("beta2", C.c_uint8 * 128)]
@@ -67,9 +72,10 @@ DKIM_SKIP_BODY_HASH = 1
 
 MAIN_EMAIL_VERIFIER, MAIN_SHA256_BYTES, MAIN_RSA_VERIFIER, MAIN_FP_MUL = 0, 1, 2, 3
 MAIN_REVEAL_SUBSTRING, MAIN_COUNT_SUBSTRING = 4, 5   # RevealSubstring(L, S, uniq), CountSubstringOccurrences(L, S): max_header = L, max_body = S, n = uniq
+MAIN_EMAIL_REVEAL = 6   # EmailReveal(...): EmailVerifier + RevealSubstring + PackBytes + EmailNullifier (zkwg_circuit_create_app)
 (IN_HEADER, IN_BODY, IN_PRECOMPUTED_SHA, IN_PUBKEY, IN_SIGNATURE, IN_MESSAGE,
  IN_HEADER_LEN, IN_BODY_LEN, IN_BODY_HASH_INDEX, IN_HEADER_MASK, IN_BODY_MASK, IN_DECODED_BODY,
- IN_RANGE_FLAGS) = range(13)
+ IN_RANGE_FLAGS, IN_SUBSTRING_START, IN_SUBSTRING_LEN) = range(15)
 
 _lib = None
 
@@ -97,6 +103,7 @@ def load():
         "zkwg_circuit_create_sym": (i32, [C.POINTER(Config), i32, C.c_char_p, u64, C.c_char_p, u64, C.POINTER(vp)]),
         "zkwg_circuit_create_full": (i32, [C.POINTER(Config), i32, C.c_char_p, u64, C.c_char_p, u64, vp, u64, C.POINTER(vp)]),
         "zkwg_circuit_create_regex": (i32, [C.POINTER(Config), i32, C.POINTER(RegexSource), C.c_char_p, u64, C.c_char_p, u64, vp, u64, C.POINTER(vp)]),
+        "zkwg_circuit_create_app": (i32, [C.POINTER(Config), C.POINTER(AppConfig), i32, C.POINTER(vp)]),
         "zkwg_regex_info": (i32, [vp, vp]),
         "zkwg_linear_rows": (u64, [vp]),
         "zkwg_layout_map": (u64, [vp, vp, u64]),
@@ -251,7 +258,7 @@ def load():
 
 
 EXPORTS = [
-    "zkwg_abi_version", "zkwg_strerror", "zkwg_circuit_create", "zkwg_circuit_create_sym", "zkwg_circuit_create_full", "zkwg_circuit_create_regex", "zkwg_regex_info", "zkwg_linear_rows", "zkwg_layout_map", "zkwg_image_layout", "zkwg_segment_table", "zkwg_inverse_table_half", "zkwg_linear_complete_host", "zkwg_o0_gather_host", "zkwg_last_error", "zkwg_circuit_destroy",
+    "zkwg_abi_version", "zkwg_strerror", "zkwg_circuit_create", "zkwg_circuit_create_sym", "zkwg_circuit_create_full", "zkwg_circuit_create_regex", "zkwg_circuit_create_app", "zkwg_regex_info", "zkwg_linear_rows", "zkwg_layout_map", "zkwg_image_layout", "zkwg_segment_table", "zkwg_inverse_table_half", "zkwg_linear_complete_host", "zkwg_o0_gather_host", "zkwg_last_error", "zkwg_circuit_destroy",
     "zkwg_witness_len", "zkwg_witness_bytes", "zkwg_num_public", "zkwg_input_stride",
     "zkwg_input_offset", "zkwg_scratch_bytes", "zkwg_scratch_bytes_standard", "zkwg_pack_input", "zkwg_pack_field", "zkwg_pack_masks", "zkwg_pack_decoded_body", "zkwg_calculate_batch",
     "zkwg_generate_inputs_device", "zkwg_stream_create_masked", "zkwg_stream_destroy", "zkwg_expand_host", "zkwg_set_host_expand", "zkwg_alloc_pinned", "zkwg_free_pinned", "zkwg_calculate_batch_device", "zkwg_prepare_device", "zkwg_expand_device", "zkwg_expand_montgomery_device", "zkwg_circuit_attach_r1cs", "zkwg_abc_bytes", "zkwg_expand_abc_device", "zkwg_expand_abc_host", "zkwg_expand_full_host", "zkwg_set_prepare_throttle", "zkwg_set_prepare_mask", "zkwg_set_timing", "zkwg_last_kernel_ms", "zkwg_timing_summary", "zkwg_num_kernels",

@@ -28,6 +28,13 @@ def circuit_kwargs(arg):
     m = re.fullmatch(r"\s*CountSubstringOccurrences\(\s*(\d+)\s*,\s*(\d+)\s*\)\s*", arg)
     if m:   # utils/array.circom:226
         return dict(main_kind=zkwg.MAIN_COUNT_SUBSTRING, max_header=int(m.group(1)), max_body=int(m.group(2)), n=0, k=0)
+    m = re.fullmatch(r"\s*EmailReveal\(([\d\s,]+)\)\s*", arg)
+    if m:   # circuits/email-reveal.circom
+        p = [int(x) for x in m.group(1).split(",")]
+        if len(p) != 9:
+            raise SystemExit("EmailReveal takes 9 parameters")
+        return dict(main_kind=zkwg.MAIN_EMAIL_REVEAL, max_header=p[0], max_body=p[1], n=p[2], k=p[3], ignore_body_hash_check=p[4],
+                    reveal_from_body=p[5], max_substring=p[6], check_uniqueness=p[7], with_nullifier=p[8])
     text = open(arg).read() if os.path.exists(arg) else arg
     kw = json.loads(text)
     base = os.path.dirname(arg) if os.path.exists(arg) else "."

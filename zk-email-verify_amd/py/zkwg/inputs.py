@@ -203,3 +203,52 @@ def generate_email_verifier_inputs(raw_email, params=None, dkim_verification_arg
         result, p.get("maxHeadersLength"), p.get("maxBodyLength"), bool(p.get("ignoreBodyHashCheck")), p.get("shaPrecomputeSelector"),
         bool(p.get("enableHeaderMasking")), p.get("headerMask"), bool(p.get("enableBodyMasking")), p.get("bodyMask"),
         bool(p.get("removeSoftLineBreaks")))
+
+
+def locate_substring(source, needle=None, start=None, length=None, check_uniqueness=True):
+    """(substringStartIndex, substringLength) of EmailReveal over `source` = the emailHeader / emailBody array the circuit sees
+    (bytes or a list of numbers): the position of `needle`, or the given start and length checked against the array.  Raises
+    ValueError when the needle is absent, or occurs more than once while the circuit checks uniqueness."""
+    src = bytes(int(b) for b in source)
+    if needle is not None:
+        needle = needle.encode() if isinstance(needle, str) else bytes(needle)
+        if not needle:
+            raise ValueError("the needle is empty")
+        at = src.find(needle)
+        if at < 0:
+            raise ValueError("the needle does not occur in what the circuit sees of the email")
+        if check_uniqueness and src.find(needle, at + 1) >= 0:
+            raise ValueError("the needle occurs more than once and the circuit checks uniqueness")
+        return at, len(needle)
+    if start is None or length is None:
+        raise ValueError("give a needle, or start and length")
+    if start < 0 or length < 0 or start + length > len(src):
+        raise ValueError("start and length do not lie inside the source")
+    return int(start), int(length)
+
+
+def generate_email_reveal_inputs_from_dkim_result(dkim, params=None, needle=None, start=None, length=None):
+    """generate_email_verifier_inputs_from_dkim_result plus substringStartIndex / substringLength of EmailReveal
+    (circuits/email-reveal.circom).  params: maxHeadersLength, maxBodyLength, ignoreBodyHashCheck, shaPrecomputeSelector as for
+    EmailVerifier, and revealFromBody, shouldCheckUniqueness (default 1)."""
+    p = dict(params or {})
+    if p.get("enableHeaderMasking") or p.get("enableBodyMasking") or p.get("removeSoftLineBreaks"):
+        raise ValueError("EmailReveal has no masking and no soft-line-break removal")
+    if p.get("revealFromBody") and p.get("ignoreBodyHashCheck"):
+        raise ValueError("revealFromBody needs the body-hash check")
+    inputs = generate_email_verifier_inputs_from_dkim_result(dkim, p.get("maxHeadersLength"), p.get("maxBodyLength"),
+                                                             bool(p.get("ignoreBodyHashCheck")), p.get("shaPrecomputeSelector"))
+    a, n = locate_substring(inputs["emailBody" if p.get("revealFromBody") else "emailHeader"], needle, start, length,
+                            bool(p.get("shouldCheckUniqueness", 1)))
+    inputs["substringStartIndex"], inputs["substringLength"] = str(a), str(n)
+    return inputs
+
+
+def generate_email_reveal_inputs(raw_eml, params=None, keys=None, needle=None, start=None, length=None, dkim_verification_args=None,
+                                 device=0):
+    """A raw email -> the CircuitInput of EmailReveal: verifyDKIMSignature, EmailVerifier's inputs, and the position of
+    `needle` (or start / length) in the canonical header or body the circuit sees."""
+    from . import dkim
+    a = dict(dkim_verification_args or {})
+    result = dkim.verify_dkim_signature(raw_eml, a.get("domain") or "", a.get("enableSanitization", True), keys=keys, device=device)
+    return generate_email_reveal_inputs_from_dkim_result(result, params, needle, start, length)

@@ -719,19 +719,22 @@ def base64_decode(g, pre, chars, byte_length=32):
 
 
 def email_verifier_constraints(symbols, N, M, enable_header_masking=0, enable_body_masking=0, remove_soft_line_breaks_flag=0,
-                               ignore_body_hash_check=0):
+                               ignore_body_hash_check=0, prefix="main"):
+    """prefix: the path of the EmailVerifier component -- "main" for the plain main, "main.ev" inside EmailReveal, where the inputs
+    are main's (the component's copies are aliases), shaHi / shaLo are not outputs and pubkeyHash is main's output."""
+    pre = prefix
     slot_of = {n: s for s, n in symbols}
     body_on = not ignore_body_hash_check
     b = Builder(slot_of)
-    _, sha = sha256_bytes_constraints(symbols, N, "main.anon_Sha256Bytes", "main.emailHeader", builder=b,
+    _, sha = sha256_bytes_constraints(symbols, N, pre + ".anon_Sha256Bytes", "main.emailHeader", builder=b,
                                                length="main.emailHeaderLength")
     if body_on:
-        _, body_sha = sha256_bytes_constraints(symbols, M, "main.anon_Sha256BytesPartial", "main.emailBody",
+        _, body_sha = sha256_bytes_constraints(symbols, M, pre + ".anon_Sha256BytesPartial", "main.emailBody",
                                                pre="main.precomputedSHA", builder=b, length="main.emailBodyLength")
     cons = b.cons
     # PackBits(256, 128) (utils/bytes.circom:194-210 via email-verifier.circom:68-71): chunk 0 -> shaHi, chunk 1 ->
     # shaLo, each chunk big-endian: out[i] = sum_j in[128 i + j] * 2^(127 - j)
-    for i, name in enumerate(("main.shaHi", "main.shaLo")):
+    for i, name in enumerate(("main.shaHi", "main.shaLo") if pre == "main" else ()):
         acc = lc_add({}, wire(slot_of[name]), -1)
         for j in range(128):
             acc = lc_add(acc, sha[128 * i + j], 1 << (127 - j))
@@ -741,41 +744,41 @@ def email_verifier_constraints(symbols, N, M, enable_header_masking=0, enable_bo
     message = [{} for _ in range(17)]
     for i in range(256):
         message[i // n] = lc_add(message[i // n], sha[255 - i], 1 << (i % n))
-    g = RsaBuilder(slot_of, "main.rsaVerifier")
+    g = RsaBuilder(slot_of, pre + ".rsaVerifier")
     g.cons = cons
     arr = lambda nm, k: [wire(slot_of[f"main.{nm}[{i}]"]) for i in range(k)]
     g.rsa_verifier(message, arr("signature", 17), arr("pubkey", 17))
     header = arr("emailHeader", N)
     hlen = wire(slot_of["main.emailHeaderLength"])
-    g.num2bits("main.n2bHeaderLength", hlen, log2ceil(N))
-    assert_zero_padding(g, "main.anon_AssertZeroPadding_header", header, hlen)
+    g.num2bits(pre + ".n2bHeaderLength", hlen, log2ceil(N))
+    assert_zero_padding(g, pre + ".anon_AssertZeroPadding_header", header, hlen)
     if not body_on:      # email-verifier.circom:108: everything below sits inside `if (ignoreBodyHashCheck != 1)`
         if enable_header_masking:
             _byte_mask(g, slot_of, header, arr("headerMask", N), "maskedHeader", "byteMask_header")
-        cons += poseidon9_constraints(symbols)
+        cons += poseidon9_constraints(symbols, pre)
         return cons
     body = arr("emailBody", M)
     blen = wire(slot_of["main.emailBodyLength"])
     bhi = wire(slot_of["main.bodyHashIndex"])
-    g.num2bits("main.n2bBodyLength", blen, log2ceil(M))
-    assert_zero_padding(g, "main.anon_AssertZeroPadding_body", body, blen)
-    match, reveal = body_hash_regex_v1(g, "main.anon_BodyHashRegex", header)
+    g.num2bits(pre + ".n2bBodyLength", blen, log2ceil(M))
+    assert_zero_padding(g, pre + ".anon_AssertZeroPadding_body", body, blen)
+    match, reveal = body_hash_regex_v1(g, pre + ".anon_BodyHashRegex", header)
     g.lin(lc_add(match, const(-1)))                                   # bhRegexMatch === 1
-    chars = select_regex_reveal(g, "main.anon_SelectRegexReveal", reveal, bhi, 44)
-    hbh = base64_decode(g, "main.anon_Base64Decode", chars)
+    chars = select_regex_reveal(g, pre + ".anon_SelectRegexReveal", reveal, bhi, 44)
+    hbh = base64_decode(g, pre + ".anon_Base64Decode", chars)
     for i in range(32):                                               # computedBodyHashInts[i].out === headerBodyHash[i]
         acc = lc_add({}, hbh[i], -1)
         for j in range(8):
             acc = lc_add(acc, body_sha[8 * i + j], 1 << (7 - j))
         g.lin(acc)
     if remove_soft_line_breaks_flag:       # email-verifier.circom:148-156
-        valid = remove_soft_line_breaks(g, "main.qpEncodingChecker", body, arr("decodedEmailBodyIn", M))
+        valid = remove_soft_line_breaks(g, pre + ".qpEncodingChecker", body, arr("decodedEmailBodyIn", M))
         g.lin(lc_add(valid, const(-1)))
     if enable_header_masking:
         _byte_mask(g, slot_of, header, arr("headerMask", N), "maskedHeader", "byteMask_header")
     if enable_body_masking:
         _byte_mask(g, slot_of, body, arr("bodyMask", M), "maskedBody", "byteMask_body")
-    cons += poseidon9_constraints(symbols)
+    cons += poseidon9_constraints(symbols, pre)
     return cons
 
 
@@ -876,16 +879,86 @@ def poseidon_constants(t):   # noqa: F811  (memoised)
     return _pos_cache[t]
 
 
-def poseidon9_constraints(symbols):
-    """The PoseidonLarge(121,17) -> Poseidon(9) block of EmailVerifier (utils/hash.circom:15-39): the last
+def poseidon_large_inputs(slot, name):
+    """poseidonInput[9] of PoseidonLarge(121, 17) over the 17-element signal array `name` (utils/hash.circom:15-39)"""
+    pk = [slot[f"{name}[{i}]"] for i in range(17)]
+    return [({pk[2 * i]: 1, pk[2 * i + 1]: 1 << 121} if i < 8 else {pk[16]: 1}) for i in range(9)]
+
+
+def poseidon9_constraints(symbols, prefix="main"):
+    """The PoseidonLarge(121,17) -> Poseidon(9) block of the EmailVerifier component `prefix` (utils/hash.circom:15-39): the last
     constraint ties the result to main.pubkeyHash."""
     slot = {n: s for s, n in symbols}
-    pk = [slot[f"main.pubkey[{i}]"] for i in range(17)]
-    inputs = [({pk[2 * i]: 1, pk[2 * i + 1]: 1 << 121} if i < 8 else {pk[16]: 1}) for i in range(9)]
     cons = []
-    out = poseidon_constraints(cons, slot, "main.anon_PoseidonLarge.anon_Poseidon", inputs)
+    out = poseidon_constraints(cons, slot, prefix + ".anon_PoseidonLarge.anon_Poseidon", poseidon_large_inputs(slot, "main.pubkey"))
     cons.append((lc_add(out, wire(slot["main.pubkeyHash"]), -1), const(1), {}))
     return cons
+
+
+# ------------------------------------------------------------------ EmailReveal (circuits/email-reveal.circom)
+MAX_BYTES_IN_FIELD = 31
+
+
+def pack_bytes(g, in_, out):
+    """PackBytes(len(in_)) (utils/bytes.circom:28-60): every intSums is a linear alias, so each output is one linear row,
+    out[i] = sum_j 256^j in[31 i + j]"""
+    assert len(out) == (len(in_) + MAX_BYTES_IN_FIELD - 1) // MAX_BYTES_IN_FIELD
+    for i, o in enumerate(out):
+        acc = lc_scale(o, -1)
+        for j, x in enumerate(in_[MAX_BYTES_IN_FIELD * i:MAX_BYTES_IN_FIELD * (i + 1)]):
+            acc = lc_add(acc, x, 1 << (8 * j))
+        g.lin(acc)
+
+
+def email_nullifier(g, pre, signature_name):
+    """EmailNullifier(121, 17) (helpers/email-nullifier.circom:15-23) as the component `pre` -> out as a linear combination:
+    Poseidon(9) over PoseidonLarge's merged limbs (t = 10), then Poseidon(1) of that hash (t = 2)"""
+    h = poseidon_constraints(g.cons, g.slot, pre + ".anon_PoseidonLarge.anon_Poseidon", poseidon_large_inputs(g.slot, signature_name), t=10)
+    return poseidon_constraints(g.cons, g.slot, pre + ".anon_Poseidon", [h], t=2)
+
+
+def email_reveal_constraints(symbols, N, M, ignore_body_hash_check, reveal_from_body, max_sub, check_uniqueness, with_nullifier):
+    """`component main = EmailReveal(N, M, 121, 17, ignore, fromBody, S, uniq, nullifier)`: EmailVerifier's constraints under
+    main.ev, RevealSubstring's under main.rs over the header or body wires, one linear row per packed output, the nullifier's
+    two Poseidon blocks and the row that ties it to its output"""
+    slot_of = {n: s for s, n in symbols}
+    cons = email_verifier_constraints(symbols, N, M, ignore_body_hash_check=ignore_body_hash_check, prefix="main.ev")
+    g = RsaBuilder(slot_of, "main.rs")
+    g.cons = cons
+    src, L = ("emailBody", M) if reveal_from_body else ("emailHeader", N)
+    in_ = [wire(slot_of[f"main.{src}[{i}]"]) for i in range(L)]
+    sub = reveal_substring(g, "main.rs", in_, wire(slot_of["main.substringStartIndex"]), wire(slot_of["main.substringLength"]),
+                           max_sub, check_uniqueness)
+    chunks = (max_sub + MAX_BYTES_IN_FIELD - 1) // MAX_BYTES_IN_FIELD
+    pack_bytes(g, sub, [wire(slot_of[f"main.revealed[{i}]"]) for i in range(chunks)])
+    if with_nullifier:
+        out = email_nullifier(g, "main.anon_EmailNullifier", "main.signature")
+        g.lin(lc_add(out, wire(slot_of["main.emailNullifier"]), -1))
+    return cons
+
+
+def email_reveal_constraint_count(N, M, ignore_body_hash_check, reveal_from_body, max_sub, check_uniqueness, with_nullifier, n_ev):
+    """constraints email_reveal_constraints emits, from n_ev = the count of the plain EmailVerifier(N, M, ..., ignore) main
+    (DESIGN.md section 26): EmailVerifier without its two shaHi / shaLo rows, RevealSubstring without its `substring <==` rows,
+    one row per packed output, 3 per S-box of Poseidon(9) and Poseidon(1) plus the output row"""
+    L = M if reveal_from_body else N
+    c = n_ev - 2
+    c += reveal_substring_constraint_count(L, max_sub, check_uniqueness) - max_sub
+    c += (max_sub + MAX_BYTES_IN_FIELD - 1) // MAX_BYTES_IN_FIELD
+    if with_nullifier:
+        c += 3 * (8 * 10 + 60) + 3 * (8 * 2 + 56) + 1
+    return c
+
+
+def email_reveal_r1cs(symbols, N, M, ignore_body_hash_check, reveal_from_body, max_sub, check_uniqueness, with_nullifier,
+                      public_rows=False):
+    """bytes of the `.r1cs` of EmailReveal over the kept-v1 wires: 1 + nullifier + chunks public outputs, no public inputs"""
+    cons = email_reveal_constraints(symbols, N, M, ignore_body_hash_check, reveal_from_body, max_sub, check_uniqueness, with_nullifier)
+    n_out = 1 + (1 if with_nullifier else 0) + (max_sub + MAX_BYTES_IN_FIELD - 1) // MAX_BYTES_IN_FIELD
+    if public_rows:
+        cons = append_public_rows(cons, n_out)
+    n_prv = N + 1 + 17 + 17 + (0 if ignore_body_hash_check else 1 + 32 + M + 1) + 2
+    return write_r1cs(len(symbols), cons, n_pub_out=n_out, n_pub_in=0, n_prv_in=n_prv)
 
 
 def remove_soft_line_breaks(g, pre, enc, dec):
@@ -1002,12 +1075,14 @@ def _main():
     import argparse
     import zkwg
     ap = argparse.ArgumentParser(description=__doc__.split("\n\n")[0])
-    ap.add_argument("--main", choices=["email-verifier", "sha256-bytes", "rsa-verifier", "reveal-substring", "count-substring"],
+    ap.add_argument("--main", choices=["email-verifier", "sha256-bytes", "rsa-verifier", "reveal-substring", "count-substring", "email-reveal"],
                     default="email-verifier",
                     help="main component (tests/test-circuits/{email-verifier,sha,rsa,reveal-substring,count-substring-occurrences}-test.circom)")
     ap.add_argument("--max-length", type=int, default=256, help="reveal-substring / count-substring: maxLength / maxLen")
     ap.add_argument("--max-substring", type=int, default=16, help="reveal-substring / count-substring: maxSubstringLength / maxSubstringLen")
     ap.add_argument("--check-uniqueness", type=int, default=1, choices=[0, 1], help="reveal-substring: shouldCheckUniqueness")
+    ap.add_argument("--reveal-from-body", type=int, default=0, choices=[0, 1], help="email-reveal: revealFromBody")
+    ap.add_argument("--with-nullifier", type=int, default=1, choices=[0, 1], help="email-reveal: withNullifier")
     ap.add_argument("--max-header", type=int, default=1024)
     ap.add_argument("--max-body", type=int, default=1536)
     ap.add_argument("--ignore-body-hash-check", type=int, default=0)
@@ -1037,6 +1112,13 @@ def _main():
         sym = c.symbols()
         data = write_r1cs(len(sym), count_substring_main_constraints(sym, a.max_length, a.max_substring),
                           n_pub_out=1, n_pub_in=0, n_prv_in=a.max_length + a.max_substring)
+    elif a.main == "email-reveal":
+        c = zkwg.Circuit(zkwg.MAIN_EMAIL_REVEAL, max_header=a.max_header, max_body=a.max_body, device=-1,
+                         ignore_body_hash_check=a.ignore_body_hash_check, reveal_from_body=a.reveal_from_body,
+                         max_substring=a.max_substring, check_uniqueness=a.check_uniqueness, with_nullifier=a.with_nullifier)
+        sym = c.symbols()
+        data = email_reveal_r1cs(sym, a.max_header, a.max_body, a.ignore_body_hash_check, a.reveal_from_body, a.max_substring,
+                                 a.check_uniqueness, a.with_nullifier, public_rows=bool(a.public_rows))
     else:
         c = zkwg.Circuit(zkwg.MAIN_EMAIL_VERIFIER, max_header=a.max_header, max_body=a.max_body, device=-1,
                          ignore_body_hash_check=a.ignore_body_hash_check,
