@@ -95,3 +95,43 @@ def test_sym_layout_on_gpu_bit_exact():
         # .wtns written in the file's order
         blob = zkwg.WitnessCalculator(c).calculateWTNSBin(inps[0])
         assert blob[:4] == b"wtns" and int.from_bytes(blob[60:64], "little") == c.W and len(blob) == 76 + 32 * c.W
+
+
+# every main that admits a `.sym` layout, at the smallest parameters the suite uses elsewhere
+_SYM_MAINS = [
+    ("sha256_bytes_64", dict(main_kind="MAIN_SHA256_BYTES", max_header=64, max_body=0)),
+    ("rsa_verifier", dict(main_kind="MAIN_RSA_VERIFIER", max_header=0, max_body=0)),
+    ("fp_mul_2_4", dict(main_kind="MAIN_FP_MUL", max_header=0, max_body=0, n=2, k=4)),
+    ("email_verifier_576_192", dict(main_kind="MAIN_EMAIL_VERIFIER", max_header=576, max_body=192)),
+]
+
+
+@pytest.mark.parametrize("name,kw", _SYM_MAINS, ids=[m[0] for m in _SYM_MAINS])
+def test_sym_layout_identity_round_trip_every_main(name, kw):
+    """The text zkwg_write_sym gives for a kept-v1 handle, fed back to zkwg_circuit_create_sym, is the identity layout:
+    zkwg_layout_map is 0..W-1, zkwg_witness_len and the names are unchanged.  Every caller of the walkers goes through
+    zk_walk_main (zkwg_build.h).  The FpMul case is new behaviour: the names the `.sym` reader collects used to come from
+    EmailVerifier's walker for an FpMul handle, so no FpMul `.sym` could match."""
+    import zkwg
+    kw = dict(kw, main_kind=getattr(zkwg, kw["main_kind"]))
+    c0 = zkwg.Circuit(device=-1, **kw)
+    sym0 = c0.symbols()
+    assert [s for s, _ in sym0] == list(range(c0.W))
+    ident = "".join(f"{s},{s},0,{n}\n" for s, n in sym0[1:])
+    c = zkwg.Circuit(device=-1, sym=ident, **kw)
+    assert c.W == c0.W and c.witness_bytes == c0.witness_bytes
+    assert c.layout_map() == list(range(c0.W))
+    assert c.symbols() == sym0
+
+
+def test_sym_layout_refused_for_the_substring_mains_and_email_reveal():
+    import zkwg
+    import emailreveal as er
+    for kw in (dict(main_kind=zkwg.MAIN_REVEAL_SUBSTRING, max_header=64, max_body=8, n=1, k=0),
+               dict(main_kind=zkwg.MAIN_COUNT_SUBSTRING, max_header=64, max_body=8, n=0, k=0)):
+        c0 = zkwg.Circuit(device=-1, **kw)
+        ident = "".join(f"{s},{s},0,{n}\n" for s, n in c0.symbols()[1:])
+        with pytest.raises(zkwg.ZkwgError, match="the substring mains have no .sym / numbered layout"):
+            zkwg.Circuit(device=-1, sym=ident, **kw)
+    with pytest.raises(zkwg.ZkwgError, match="EmailReveal has no .sym / numbered layout"):
+        zkwg.Circuit(device=-1, sym="1,1,0,main.x\n", **er.circuit_kwargs("A"))

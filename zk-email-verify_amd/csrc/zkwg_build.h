@@ -42,6 +42,21 @@ static inline void zk_build_entries(u64 W, const std::vector<ZkSeg>& segs, std::
     } else e.type = ZSEG_NTYPES;
   }
 }
+// The one place that knows the mains: main_kind -> its walker, with the parameters taken from the schedule (s.fpg.n / k,
+// s.sub.L / S / uniq, s.app -- build_sched fills them before it walks).  build_sched, zk_collect_names and zkwg_write_sym all
+// come through here; a new main is registered here and gets its parameter rules in build_sched's switch.
+static inline void zk_walk_main(ZkWalker& w, ZkSched& s) {
+  switch (s.main_kind) {
+    case ZKWG_MAIN_SHA256_BYTES: zk_walk_main_sha(w, s); break;
+    case ZKWG_MAIN_RSA_VERIFIER: zk_walk_main_rsa(w, s); break;
+    case ZKWG_MAIN_FP_MUL: zk_walk_main_fpmul(w, s, s.fpg.n, s.fpg.k); break;
+    case ZKWG_MAIN_REVEAL_SUBSTRING: zk_walk_main_reveal(w, s, s.sub.L, s.sub.S, s.sub.uniq); break;
+    case ZKWG_MAIN_COUNT_SUBSTRING: zk_walk_main_count(w, s, s.sub.L, s.sub.S); break;
+    case ZKWG_MAIN_EMAIL_VERIFIER: zk_walk_main_ev(w, s); break;
+    case ZKWG_MAIN_EMAIL_REVEAL: zk_walk_main_app(w, s); break;
+    default: break;      // (build_sched refuses an unknown main before it walks)
+  }
+}
 static bool build_sched(const zkwg_config& cfg, ZkSched& s, std::vector<ZkSeg>& segs, const zkc::Net* net = nullptr,
                         const zkwg_app_config* app = nullptr) {
   memset(&s, 0, sizeof(s));
@@ -111,15 +126,16 @@ static bool build_sched(const zkwg_config& cfg, ZkSched& s, std::vector<ZkSeg>& 
   if (net && (cfg.main_kind != ZKWG_MAIN_EMAIL_VERIFIER || cfg.ignore_body_hash_check || net->n_in != cfg.max_header)) return false;
   u64 max_small = 256;  // largest |d| whose inverse zk_expand looks up
   if (net) max_small = std::max<u64>(max_small, (u64)net->inv_need + 1);
-  switch (cfg.main_kind) {
+  switch (cfg.main_kind) {   // each main: its parameter rules, what its walker takes from the schedule, the walk (zk_walk_main), max_small
     case ZKWG_MAIN_SHA256_BYTES:
       if (cfg.max_header == 0) return false;
       s.nframes = 1;
       init_frame(s.fr[0], cfg.max_header, 0, s.in_off[ZKWG_IN_HEADER], s.in_off[ZKWG_IN_HEADER_LEN]);
-      zk_walk_main_sha(w, s);
+      zk_walk_main(w, s);
       max_small = std::max<u64>(max_small, s.fr[0].nblocks + 2);
       break;
     case ZKWG_MAIN_EMAIL_VERIFIER:
+    case ZKWG_MAIN_EMAIL_REVEAL:      // EmailVerifier's frames and bounds, with its ZkAppLayout and the uniqueness bound on top
       if (cfg.n != 121 || cfg.k != 17 || cfg.max_header < 128) return false;
       s.body = cfg.ignore_body_hash_check ? 0 : 1;
       if (s.body && cfg.max_body == 0) return false;
@@ -127,7 +143,18 @@ static bool build_sched(const zkwg_config& cfg, ZkSched& s, std::vector<ZkSeg>& 
       init_frame(s.fr[0], cfg.max_header, 0, s.in_off[ZKWG_IN_HEADER], s.in_off[ZKWG_IN_HEADER_LEN]);
       if (s.body) init_frame(s.fr[1], cfg.max_body, 1, s.in_off[ZKWG_IN_BODY], s.in_off[ZKWG_IN_BODY_LEN]);
       w.sha_rounds = true;   // the flagship's image: 800 bytes of round states per SHA block instead of the 7,616-byte trace
-      zk_walk_main_ev(w, s);
+      if (app) {
+        ZkAppLayout& A = s.app;
+        A.present = 1; A.from_body = app->reveal_from_body; A.S = app->max_substring;
+        A.chunks = (A.S + ZK_APP_PACK - 1) / ZK_APP_PACK;
+        A.nullifier = app->with_nullifier;
+        A.in_src = s.in_off[A.from_body ? ZKWG_IN_BODY : ZKWG_IN_HEADER];
+        A.src_len = A.from_body ? cfg.max_body : cfg.max_header;
+        A.in_start = s.in_off[ZKWG_IN_SUBSTRING_START]; A.in_len = s.in_off[ZKWG_IN_SUBSTRING_LEN];
+        A.in_sig = s.in_off[ZKWG_IN_SIGNATURE];
+        s.sub.uniq = app->check_uniqueness;
+      }
+      zk_walk_main(w, s);
       max_small = std::max<u64>(max_small, 2100);
       max_small = std::max<u64>(max_small, (u64)cfg.max_header + 64);
       // SelectRegexReveal's IsEqual(i, startIndex): every startIndex its range checks admit
@@ -135,54 +162,33 @@ static bool build_sched(const zkwg_config& cfg, ZkSched& s, std::vector<ZkSeg>& 
       // maxHeadersLength that is not a power of two
       if (s.body) max_small = std::max<u64>(max_small, 1ull << s.sel_bits);
       max_small = std::max<u64>(max_small, std::max(s.fr[0].nblocks, s.fr[1].nblocks) + 2);
-      break;
-    case ZKWG_MAIN_EMAIL_REVEAL: {
-      if (cfg.n != 121 || cfg.k != 17 || cfg.max_header < 128) return false;
-      s.body = cfg.ignore_body_hash_check ? 0 : 1;
-      if (s.body && cfg.max_body == 0) return false;
-      s.nframes = s.body ? 2 : 1;
-      init_frame(s.fr[0], cfg.max_header, 0, s.in_off[ZKWG_IN_HEADER], s.in_off[ZKWG_IN_HEADER_LEN]);
-      if (s.body) init_frame(s.fr[1], cfg.max_body, 1, s.in_off[ZKWG_IN_BODY], s.in_off[ZKWG_IN_BODY_LEN]);
-      w.sha_rounds = true;
-      ZkAppLayout& A = s.app;
-      A.present = 1; A.from_body = app->reveal_from_body; A.S = app->max_substring;
-      A.chunks = (A.S + ZK_APP_PACK - 1) / ZK_APP_PACK;
-      A.nullifier = app->with_nullifier;
-      A.in_src = s.in_off[A.from_body ? ZKWG_IN_BODY : ZKWG_IN_HEADER];
-      A.src_len = A.from_body ? cfg.max_body : cfg.max_header;
-      A.in_start = s.in_off[ZKWG_IN_SUBSTRING_START]; A.in_len = s.in_off[ZKWG_IN_SUBSTRING_LEN];
-      A.in_sig = s.in_off[ZKWG_IN_SIGNATURE];
-      s.sub.uniq = app->check_uniqueness;
-      zk_walk_main_app(w, s);
-      max_small = std::max<u64>(max_small, 2100);
-      max_small = std::max<u64>(max_small, (u64)cfg.max_header + 64);
-      if (s.body) max_small = std::max<u64>(max_small, 1ull << s.sel_bits);
-      max_small = std::max<u64>(max_small, std::max(s.fr[0].nblocks, s.fr[1].nblocks) + 2);
       // IsZero(difference[j]): |(in - substring) substring| reaches 255 * 255 (utils/array.circom:211-212)
-      if (s.sub.uniq) max_small = std::max<u64>(max_small, 255 * 255);
+      if (app && s.sub.uniq) max_small = std::max<u64>(max_small, 255 * 255);
       break;
-    }
     case ZKWG_MAIN_RSA_VERIFIER:
       if (cfg.n != 121 || cfg.k != 17) return false;
       s.nframes = 0;
-      zk_walk_main_rsa(w, s);
+      zk_walk_main(w, s);
       max_small = std::max<u64>(max_small, 2100);
       break;
     case ZKWG_MAIN_FP_MUL:
       // generic parameters, as long as the numbers fit machine words (zkwg_fpmul_core.h); (121, 17) lives in the RSA path
       if (cfg.n < 1 || cfg.k < 2 || cfg.k > 17 || (u64)cfg.n * cfg.k > 62 || cfg.max_header || cfg.max_body) return false;
       s.nframes = 0;
-      zk_walk_main_fpmul(w, s, cfg.n, cfg.k);
+      s.fpg.n = cfg.n; s.fpg.k = cfg.k;
+      zk_walk_main(w, s);
       break;
     case ZKWG_MAIN_REVEAL_SUBSTRING:
       s.nframes = 0;
-      zk_walk_main_reveal(w, s, cfg.max_header, cfg.max_body, cfg.n);
+      s.sub.L = cfg.max_header; s.sub.S = cfg.max_body; s.sub.uniq = cfg.n;
+      zk_walk_main(w, s);
       // IsZero(difference[j]): |(in - substring) substring| reaches 255 * 255 (utils/array.circom:211-212)
       if (cfg.n) max_small = 255 * 255;
       break;
     case ZKWG_MAIN_COUNT_SUBSTRING:
       s.nframes = 0;
-      zk_walk_main_count(w, s, cfg.max_header, cfg.max_body);
+      s.sub.L = cfg.max_header; s.sub.S = cfg.max_body;
+      zk_walk_main(w, s);
       max_small = 255 * 255;
       break;
     default:
@@ -250,14 +256,7 @@ static inline void zk_collect_names(ZkSched tmp, std::vector<std::string>& names
   w.names = true;
   names.assign(tmp.W, std::string());
   w.sink = [&](u64 slot, const std::string& name) { if (slot < names.size()) names[slot] = name; };
-  switch (tmp.main_kind) {
-    case ZKWG_MAIN_SHA256_BYTES: zk_walk_main_sha(w, tmp); break;
-    case ZKWG_MAIN_RSA_VERIFIER: zk_walk_main_rsa(w, tmp); break;
-    case ZKWG_MAIN_REVEAL_SUBSTRING: zk_walk_main_reveal(w, tmp, tmp.sub.L, tmp.sub.S, tmp.sub.uniq); break;
-    case ZKWG_MAIN_COUNT_SUBSTRING: zk_walk_main_count(w, tmp, tmp.sub.L, tmp.sub.S); break;
-    case ZKWG_MAIN_EMAIL_REVEAL: zk_walk_main_app(w, tmp); break;
-    default: zk_walk_main_ev(w, tmp); break;
-  }
+  zk_walk_main(w, tmp);
 }
 static bool zk_sym_layout(const ZkSched& s, const char* text, u64 len, const char* alias, u64 alias_len, ZkSymLayout& L,
                           const zkc::Net* net = nullptr) {

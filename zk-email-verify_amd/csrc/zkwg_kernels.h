@@ -27,9 +27,8 @@ __global__ void zk_r1cs_check(const u64* row_ptr, const u32* wire, const Fr* coe
                               const u8* wit, u64 stride, unsigned long long* first_bad);  // zkwg_kernels_r1cs.hip
 __global__ void zk_r1cs_eval(const u64* row_ptr, const u32* wire, const Fr* coef, const u8* kind, u32 m, const u8* wit, u64 stride,
                              u8* out, u64 out_stride, int mont);  // zkwg_kernels_r1cs.hip
-// zkwg_kernels_expand3.hip: one piece of 256 K slots per workgroup, standard / Montgomery form; K slots per lane:
-#define ZK_X3_SLOTS 4      // kept-v1 / `.sym` layouts (32 KiB pieces)
-#define ZK_X3_SLOTS_O0 1   // numbered circuits and A.w | B.w | C.w, from per-wire descriptors (8 KiB pieces, emails in batches of 4)
+// zkwg_kernels_expand3.hip: one piece of 256 K slots per workgroup, standard / Montgomery form; K slots per lane: ZK_X3_SLOTS,
+// ZK_X3_SLOTS_O0 (zkwg_sched.h)
 __global__ void zk_expand3(ZkX3 A); __global__ void zk_expand3_mont(ZkX3 A);
 __global__ void zk_expand3_o0(ZkX3 A, ZkO0Dev O); __global__ void zk_expand3_o0_mont(ZkX3 A, ZkO0Dev O);
 __global__ void zk_image_to_mont(ZkX3 A);

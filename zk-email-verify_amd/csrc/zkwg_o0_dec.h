@@ -1,6 +1,6 @@
 // Decoding of the per-wire descriptors of a numbered layout (zkwg_o0.h) into slot codes, and of codes into integers / field
 // elements: shared by the device kernels (zkwg_kernels_expand3.hip) and the host evaluation of the same tables
-// (zkwg_abc_host in zkwg_api.hip: layout-only handles, tests).
+// (tables_host in zkwg_hostpath_api.hip: layout-only handles, tests).
 #pragma once
 #include "zkwg_expand_dec.h"
 #include "zkwg_o0.h"

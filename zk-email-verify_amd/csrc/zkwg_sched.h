@@ -128,6 +128,9 @@ ZK_HD u32 zk_seg_period(const ZkSeg& g) {
 // zk_expand works in pieces of 256 K slots (K = ZK_X3_SLOTS = 4: 32 KiB of output), one per workgroup.  One table entry per piece:
 // a piece inside a single segment carries that segment's parameters (type < ZSEG_NTYPES) and the logical index of its
 // first slot; a piece that straddles segments (type = ZSEG_NTYPES) names the first segment to look at.
+// K slots per lane (zkwg_kernels_expand3.hip; the host sizes its piece tables with the same numbers):
+#define ZK_X3_SLOTS 4      // kept-v1 / `.sym` layouts (32 KiB pieces)
+#define ZK_X3_SLOTS_O0 1   // numbered circuits and A.w | B.w | C.w, from per-wire descriptors (8 KiB pieces, emails in batches of 4)
 struct ZkPortionEntry {
   u32 type, src, a, b, c, magic;
   u32 r_start;
