@@ -60,7 +60,7 @@ extern "C" {
  * Added since without breaking 2: zkwg_expand_host / zkwg_set_host_expand, zkwg_circuit_attach_r1cs / zkwg_expand_abc_device /
  * zkwg_expand_abc_host / zkwg_abc_bytes, ZKWG_MAIN_FP_MUL, ZKWG_MAIN_REVEAL_SUBSTRING, ZKWG_MAIN_COUNT_SUBSTRING,
  * ZKWG_MAIN_EMAIL_REVEAL with zkwg_app_config / zkwg_circuit_create_app and the record fields ZKWG_IN_SUBSTRING_START /
- * ZKWG_IN_SUBSTRING_LEN (ZKWG_IN_NFIELDS = 15; they take no room in the records of the other mains). */
+ * ZKWG_IN_SUBSTRING_LEN (ZKWG_IN_NFIELDS = 15; they take no room in the records of the other mains), ZKWG_MAIN_CLEAN_EMAIL_ADDRESS. */
 #define ZKWG_ABI_VERSION 3
 
 /* `component main = ...` choices (the reference's own test mains). */
@@ -79,10 +79,17 @@ enum zkwg_main_kind {
                                    count-substring-occurrences-test.circom:5: (1024, 128)).  max_header = maxLen, max_body =
                                    maxSubstringLen, n = k = 0; 2 <= max_body <= max_header <= 65536.  in[] in ZKWG_IN_HEADER, substring[] in
                                    ZKWG_IN_BODY.  Both mains: elements are bytes; no `.sym` layout, no Montgomery-form output (BAD_CONFIG) */
-  ZKWG_MAIN_EMAIL_REVEAL = 6    /* EmailReveal(maxHeader, maxBody, n, k, ignoreBodyHashCheck, revealFromBody, maxSubstringLength,
+  ZKWG_MAIN_EMAIL_REVEAL = 6,   /* EmailReveal(maxHeader, maxBody, n, k, ignoreBodyHashCheck, revealFromBody, maxSubstringLength,
                                    shouldCheckUniqueness, withNullifier), no public inputs (zk-email-verify_amd/circuits/email-reveal.circom):
                                    EmailVerifier + RevealSubstring over the header or the body + PackBytes of the revealed bytes +
                                    EmailNullifier(signature).  Created with zkwg_circuit_create_app only */
+  ZKWG_MAIN_CLEAN_EMAIL_ADDRESS = 7 /* CleanEmailAddress(maxLength), no public inputs, output isValid (utils/email.circom:16-140,
+                                   clean-email-address-test.circom:5: (32)).  max_header = max_body = maxLength, a multiple of 8 with
+                                   8 <= maxLength <= 1024 (every chunk of PoseidonModular(2 maxLength) is a Poseidon(16)); n = k = 0, every
+                                   flag 0.  encoded[] in ZKWG_IN_HEADER, decoded[] in ZKWG_IN_BODY (the record pads both slots); elements are
+                                   bytes.  The template asserts nothing: every byte input has a witness (status 4 only for a record whose
+                                   range flags are set).  No `.sym` layout, no attached constraint system, no Montgomery-form output
+                                   (BAD_CONFIG) */
 };
 
 /* Witness layouts.  KEPT_V1 is the compact layout documented in DESIGN.md; SYM is KEPT_V1 re-ordered
@@ -91,8 +98,10 @@ enum zkwg_layout { ZKWG_LAYOUT_KEPT_V1 = 0, ZKWG_LAYOUT_SYM = 1 };
 
 typedef struct zkwg_config {
   uint32_t main_kind;                /* enum zkwg_main_kind */
-  uint32_t max_header;               /* maxHeadersLength (multiple of 64); substring mains: maxLength / maxLen, any value up to 65536 */
-  uint32_t max_body;                 /* maxBodyLength   (multiple of 64; 0 if unused); substring mains: maxSubstringLength / maxSubstringLen */
+  uint32_t max_header;               /* maxHeadersLength (multiple of 64); substring mains: maxLength / maxLen, any value up to 65536;
+                                        ZKWG_MAIN_CLEAN_EMAIL_ADDRESS: maxLength */
+  uint32_t max_body;                 /* maxBodyLength   (multiple of 64; 0 if unused); substring mains: maxSubstringLength / maxSubstringLen;
+                                        ZKWG_MAIN_CLEAN_EMAIL_ADDRESS: maxLength again */
   uint32_t n;                        /* bits per RSA limb   (121); ZKWG_MAIN_REVEAL_SUBSTRING: shouldCheckUniqueness (0 / 1) */
   uint32_t k;                        /* number of RSA limbs (17)  */
   uint32_t ignore_body_hash_check;   /* template flag, email-verifier.circom:42 */
@@ -104,8 +113,8 @@ typedef struct zkwg_config {
 
 /* Fields of one packed input record (one record per email). */
 enum zkwg_input_field {
-  ZKWG_IN_HEADER = 0,         /* u8[max_header]  emailHeader / paddedIn / in (substring mains) */
-  ZKWG_IN_BODY = 1,           /* u8[max_body]    emailBody / substring (ZKWG_MAIN_COUNT_SUBSTRING) */
+  ZKWG_IN_HEADER = 0,         /* u8[max_header]  emailHeader / paddedIn / in (substring mains) / encoded (ZKWG_MAIN_CLEAN_EMAIL_ADDRESS) */
+  ZKWG_IN_BODY = 1,           /* u8[max_body]    emailBody / substring (ZKWG_MAIN_COUNT_SUBSTRING) / decoded (ZKWG_MAIN_CLEAN_EMAIL_ADDRESS) */
   ZKWG_IN_PRECOMPUTED_SHA = 2,/* u8[32]          precomputedSHA                    */
   ZKWG_IN_PUBKEY = 3,         /* 17 x 16-byte LE limbs: pubkey / modulus           */
   ZKWG_IN_SIGNATURE = 4,      /* 17 x 16-byte LE limbs                             */
@@ -374,7 +383,8 @@ int zkwg_expand_device(zkwg_circuit_t* c, const void* d_packed_inputs, uint64_t 
 int zkwg_set_prepare_throttle(zkwg_circuit_t* c, int rsa_wavefronts_per_cu);
 /* Measurement aid (tools/beside.py): zkwg_prepare_device launches only the kernels whose bit is
  * set -- bit 0 zk_sha_chain, 1 zk_sha_trace, 2 zk_net_eval, 3 zk_misc_ev, 4 zk_rsa, 5 zk_poseidon9*, 6 zk_rslb_chunks,
- * 7 zk_rslb_chain, 8 the row kernels of numbered / constraint-attached handles, 9 zk_app_tail (zk_substr shares bit 4).  Default 0xffffffff (everything); with a
+ * 7 zk_rslb_chain, 8 the row kernels of numbered / constraint-attached handles, 9 zk_app_tail (zk_substr shares bit 4, zk_cea_chunks
+ * bit 6, zk_cea_tail bit 7).  Default 0xffffffff (everything); with a
  * partial mask the images of the batch are NOT complete, so only timing may be taken from such a call. */
 int zkwg_set_prepare_mask(zkwg_circuit_t* c, uint32_t kernel_mask);
 

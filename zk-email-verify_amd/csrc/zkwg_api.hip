@@ -168,7 +168,14 @@ static int create_impl(const zkwg_config* cfg_in, int device, const char* sym_te
     fprintf(stderr, "[zkwg] create: %-28s %7.2f s\n", what, std::chrono::duration<double>(now - t_last).count());
     t_last = now;
   };
-  if (!build_sched(*cfg, c->lay.s, c->lay.segs, net, app)) { g_last_error = "unsupported circuit configuration"; return ZKWG_RC_BAD_CONFIG; }
+  if (!build_sched(*cfg, c->lay.s, c->lay.segs, net, app)) {
+    g_last_error = "unsupported circuit configuration";
+    if (cfg->main_kind == ZKWG_MAIN_CLEAN_EMAIL_ADDRESS)
+      g_last_error = !zk_cea_length_ok(cfg->max_header) ? "CleanEmailAddress: maxLength must be a multiple of 8 with 8 <= maxLength <= 1024"
+                     : cfg->max_body != cfg->max_header ? "CleanEmailAddress: max_body must equal max_header (both are maxLength)"
+                                                        : "CleanEmailAddress: n, k and every flag must be 0";
+    return ZKWG_RC_BAD_CONFIG;
+  }
   if (c->rx.net) {   // how a slot of the template's region is decoded, with host pointers (host expansion, layout-only handles); the device copy follows
     ZkNetDec& D = c->rx.h_netd;
     D.pd = c->rx.net->pd.data(); D.tab = c->rx.net->tabs.data();
@@ -177,6 +184,7 @@ static int create_impl(const zkwg_config* cfg_in, int device, const char* sym_te
   }
   if (getenv("ZKWG_DEBUG_SKIP_INV") && atoi(getenv("ZKWG_DEBUG_SKIP_INV")) && c->lay.s.rsa.present) c->lay.s.rsa.present = 2;  // profiling only
   if (c->lay.s.sub.present && (sym_text || r1cs)) { g_last_error = "the substring mains have no .sym / numbered layout"; return ZKWG_RC_BAD_CONFIG; }
+  if (c->lay.s.cea.present && (sym_text || r1cs)) { g_last_error = "CleanEmailAddress has no .sym / numbered layout"; return ZKWG_RC_BAD_CONFIG; }
   if (sym_text) {
     ZkSymLayout L;
     L.allow_holes = r1cs != nullptr;
@@ -283,6 +291,7 @@ static int create_impl(const zkwg_config* cfg_in, int device, const char* sym_te
     c->tm.kname[k++] = "zk_poseidon9";
     if (c->lay.s.app.present) { c->tm.kname[k++] = "zk_substr"; c->tm.kname[k++] = "zk_app_tail"; }
     if (c->lay.s.rslb) { c->tm.kname[k++] = "zk_rslb_chunks"; c->tm.kname[k++] = "zk_rslb_chain"; }
+    if (c->lay.s.cea.present) { c->tm.kname[k++] = "zk_cea_chunks"; c->tm.kname[k++] = "zk_cea_tail"; }
     c->tm.n_kernels = k + 1;
     for (int i = 0; i < k; ++i) c->tm.kslots[i] = 0;
   }
@@ -358,7 +367,7 @@ static int create_impl(const zkwg_config* cfg_in, int device, const char* sym_te
       }
       if (ok) c->tab.d_pos = TM.up(t10);
     }
-    if (ok && c->lay.s.rslb) {
+    if (ok && (c->lay.s.rslb || c->lay.s.cea.present)) {   // PoseidonModular: Poseidon(16) chunks, Poseidon(2) merges
       std::vector<Fr> C, M, t16, t2;
       build_poseidon_constants(17, 8, 68, C, M);
       ok = zk_build_poseidon_sparse(17, 68, C, M, t16);
@@ -371,7 +380,7 @@ static int create_impl(const zkwg_config* cfg_in, int device, const char* sym_te
       l29.insert(l29.end(), l29_2.begin(), l29_2.end());
       if (ok) c->tab.d_pos_l29 = TM.up(l29);
       { const char* v = getenv("ZKWG_RSLB_CONST_CHUNKS");
-        if (ok && !(v && atoi(v) == 0)) {
+        if (ok && c->lay.s.rslb && !(v && atoi(v) == 0)) {
           // Poseidon(16)(0, ..., 0): the same evaluator on the host (element j, limb l at st[l * 17 + j])
           std::vector<u32> st0(9 * 17, 0u);
           std::vector<Fr> z(ZK_P16_KEPT + 1);
@@ -621,6 +630,7 @@ int zkwg_circuit_attach_r1cs(zkwg_circuit_t* c, const uint8_t* r1cs, uint64_t le
   std::lock_guard<std::mutex> lock(c->dev_mutex);
   if (c->abc.m) { g_last_error = "attach_r1cs: the handle already has a constraint system"; return ZKWG_RC_BAD_CONFIG; }
   if (c->lay.s.sub.present) { g_last_error = "attach_r1cs: not available for the substring mains and EmailReveal"; return ZKWG_RC_BAD_CONFIG; }
+  if (c->lay.s.cea.present) { g_last_error = "attach_r1cs: not available for CleanEmailAddress"; return ZKWG_RC_BAD_CONFIG; }
   try {
     ZkR1csHost R;
     if (!zk_r1cs_parse(r1cs, len, R)) { g_last_error = "the .r1cs file could not be parsed: " + R.err; return ZKWG_RC_BAD_CONFIG; }

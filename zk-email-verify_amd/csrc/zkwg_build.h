@@ -54,9 +54,12 @@ static inline void zk_walk_main(ZkWalker& w, ZkSched& s) {
     case ZKWG_MAIN_COUNT_SUBSTRING: zk_walk_main_count(w, s, s.sub.L, s.sub.S); break;
     case ZKWG_MAIN_EMAIL_VERIFIER: zk_walk_main_ev(w, s); break;
     case ZKWG_MAIN_EMAIL_REVEAL: zk_walk_main_app(w, s); break;
+    case ZKWG_MAIN_CLEAN_EMAIL_ADDRESS: zk_walk_main_cea(w, s, s.cea.L); break;
     default: break;      // (build_sched refuses an unknown main before it walks)
   }
 }
+// CleanEmailAddress(maxLength): the lengths this schedule takes (include/zkwg.h ZKWG_MAIN_CLEAN_EMAIL_ADDRESS)
+static inline bool zk_cea_length_ok(u32 L) { return L >= 8 && L <= 1024 && L % 8 == 0; }
 static bool build_sched(const zkwg_config& cfg, ZkSched& s, std::vector<ZkSeg>& segs, const zkc::Net* net = nullptr,
                         const zkwg_app_config* app = nullptr) {
   memset(&s, 0, sizeof(s));
@@ -78,6 +81,9 @@ static bool build_sched(const zkwg_config& cfg, ZkSched& s, std::vector<ZkSeg>& 
     if (cfg.max_header > 65536 || cfg.max_body < 2 || cfg.max_body > cfg.max_header || cfg.k || cfg.ignore_body_hash_check ||
         cfg.remove_soft_line_breaks || net) return false;
     if (cfg.main_kind == ZKWG_MAIN_REVEAL_SUBSTRING ? (cfg.max_body == cfg.max_header || cfg.n > 1) : cfg.n != 0) return false;
+  } else if (cfg.main_kind == ZKWG_MAIN_CLEAN_EMAIL_ADDRESS) {
+    // maxLength a multiple of 8: 2 maxLength is a multiple of 16 and every chunk of PoseidonModular is a Poseidon(16)
+    if (!zk_cea_length_ok(cfg.max_header) || cfg.max_body != cfg.max_header || cfg.n || cfg.k || cfg.ignore_body_hash_check || net) return false;
   } else if (cfg.max_header % 64 != 0 || cfg.max_body % 64 != 0) return false;
   s.main_kind = cfg.main_kind;
   s.n = cfg.n; s.k = cfg.k; s.ignore_body = cfg.ignore_body_hash_check;
@@ -190,6 +196,11 @@ static bool build_sched(const zkwg_config& cfg, ZkSched& s, std::vector<ZkSeg>& 
       s.sub.L = cfg.max_header; s.sub.S = cfg.max_body;
       zk_walk_main(w, s);
       max_small = 255 * 255;
+      break;
+    case ZKWG_MAIN_CLEAN_EMAIL_ADDRESS:      // (IsEqual differences lie in [43 - 255, 64]: the default table serves)
+      s.nframes = 0;
+      s.cea.L = cfg.max_header;
+      zk_walk_main(w, s);
       break;
     default:
       return false;

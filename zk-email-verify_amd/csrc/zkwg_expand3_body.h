@@ -1,5 +1,5 @@
 // The body of zk_expand (zkwg_kernels_expand3.hip: what the kernel does and why it has this shape), in a header so that the
-// substring mains can instantiate it with their own decoder beside the common ones (SUBM = true: zk_expand3_subm,
+// substring mains and CleanEmailAddress can instantiate it with their own decoder beside the common ones (SUBM = true: zk_expand3_subm,
 // zkwg_kernels_substr.hip) without adding a case to the headline kernel's switch.
 #pragma once
 #include "zkwg_expand_dec.h"
@@ -115,7 +115,7 @@ __device__ __forceinline__ void zk_x3_store(const ZkX3& A, const ZkCtx& cx, u32 
     if (64u * j + lane < left) dst[64u * j + lane] = v[j];
 }
 
-template <bool MONT, int K, bool SUBM = false>
+template <bool MONT, int K, bool SUBM = false, bool CEA = false>
 __device__ __forceinline__ void zk_expand3_body(const ZkX3& A) {
   constexpr u32 SLOTS = 256u * K;
   const u32 unit = zk_x3_unit(A.xcd_remap);
@@ -131,7 +131,7 @@ __device__ __forceinline__ void zk_expand3_body(const ZkX3& A) {
     // the whole piece lies inside one segment: its parameters came with the entry
     ZkSeg sg;
     sg.slot = 0; sg.nslots = 0; sg.type = en.type; sg.src = en.src; sg.a = en.a; sg.b = en.b; sg.c = en.c; sg.r0 = 0; sg.pad = en.magic;
-    zk_decode_k<K, SUBM>(sg, en.r_start, 64u * K * wv + lane, nsl, cx, code);
+    zk_decode_k<K, SUBM, CEA>(sg, en.r_start, 64u * K * wv + lane, nsl, cx, code);
   } else {
     // the piece straddles segments: find each slot's
 #pragma unroll
@@ -143,7 +143,7 @@ __device__ __forceinline__ void zk_expand3_body(const ZkX3& A) {
         for (u32 si = en.first_seg; si < A.nsegs; ++si) {
           const ZkSeg sg = A.segs[si];
           if (sg.slot > slot) break;
-          if (slot < sg.slot + sg.nslots) { code[k] = zk_decode_any<SUBM>(sg, (u32)(slot - sg.slot) + sg.r0, cx); break; }
+          if (slot < sg.slot + sg.nslots) { code[k] = zk_decode_any<SUBM, CEA>(sg, (u32)(slot - sg.slot) + sg.r0, cx); break; }
         }
       }
     }

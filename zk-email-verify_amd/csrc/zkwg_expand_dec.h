@@ -339,6 +339,36 @@ struct ZkDecSubm {
   }
 };
 
+// CleanEmailAddress(L) byte-derived arrays (utils/email.circom:55-103; zkwg_layout.h zk_walk_cea): every one of them is a function of
+// the byte encoded[i], the index P of the first '+' and the index A of the first '@' (L where there is none; zk_cea_tail leaves the two
+// in small[b], small[b + 1]).  isLocalPart[i] = i < min(P, A), afterPlus[i] = i < P, afterAt[i] = i < A, hasAliasPart = P < L, and
+// the template's literal inAliasPartTemp = afterAt - afterPlus is -1 on A <= i < P (an '@' in front of the first '+').
+struct ZkDecCea {
+  const u8* __restrict__ enc; u32 kind, i0, L, P, A; int half;
+  ZK_DEC ZkDecCea(const ZkSeg& sg, const ZkCtx& cx)
+      : enc(cx.rec + sg.src), kind(sg.a & 0xffu), i0(sg.a >> 8), L(sg.c), P(cx.small[sg.b]), A(cx.small[sg.b + 1]), half(cx.half) {}
+  ZK_DEC u32 operator()(u32 r) const {
+    if (kind == ZCEA_EQ2 || kind == ZCEA_EQP) {
+      // IsEqual()([encoded[i], K]): isz.in = K - encoded[i] (circomlib comparators.circom: in[1] - in[0])
+      const u32 q = kind == ZCEA_EQ2 ? r >> 2 : r >> 1;
+      const int K = kind == ZCEA_EQP ? 46 : ((r & 2u) ? 64 : 43);
+      const int d = K - (int)enc[q];
+      return (r & 1u) ? zk_inv_code(d, half) : (u32)(d == 0);
+    }
+    const u32 i = r + i0, b = enc[i];
+    const u32 local = (u32)(i < P && i < A);
+    if (kind == ZCEA_PAA) return (u32)(b != 43u && b != 64u);
+    if (kind == ZCEA_LOCAL) return local;
+    if (kind == ZCEA_LPER) return local & (u32)(b == 46u);
+    if (kind == ZCEA_APLUS) return (u32)(i < P);
+    if (kind == ZCEA_AAT) return (u32)(i < A);
+    const int alias = P < L ? (int)(i < A) - (int)(i < P) : 0;          // inAliasPart = hasAliasPart * inAliasPartTemp
+    if (kind == ZCEA_ALIAS) return alias >= 0 ? (u32)alias : (ZK_REF_MINUS | 1u);
+    const int rm = (int)(local & (u32)(b == 46u)) + alias;               // shouldRemove in {-1, 0, 1}
+    return (u32)(1 - rm) * b;                                            // processed[i]
+  }
+};
+
 // every segment type with its decoder: ZK_FOR_SEG_TYPES(X) expands X(type, Decoder) once per type
 #define ZK_FOR_SEG_TYPES(X)                                                                                           \
   X(ZSEG_SMALL, ZkDecSmall) X(ZSEG_FR, ZkDecFr) X(ZSEG_BITS, ZkDecBits)                                                \
@@ -350,15 +380,17 @@ struct ZkDecSubm {
   X(ZSEG_SHAR_SP, ZkDecShaR<ZSEG_SHAR_SP>) X(ZSEG_SHAR_T1, ZkDecShaR<ZSEG_SHAR_T1>) X(ZSEG_SHAR_T2, ZkDecShaR<ZSEG_SHAR_T2>) \
   X(ZSEG_SHAR_SUM, ZkDecShaR<ZSEG_SHAR_SUM>)
 #define ZK_COMMA ,
-// ZSEG_SUBM stays out of the common switch: zk_expand3's register budget (64 VGPRs, 8 wavefronts per SIMD) and rate are held as they
-// are; the substring mains expand through their own instantiation (SUBM = true: zk_expand3_subm, the host expansion)
-#define ZK_FOR_SEG_TYPES_ALL(X) ZK_FOR_SEG_TYPES(X) X(ZSEG_SUBM, ZkDecSubm)
+// ZSEG_SUBM and ZSEG_CEA stay out of the common switch: zk_expand3's register budget (64 VGPRs, 8 wavefronts per SIMD) and rate are held
+// as they are; the substring mains and CleanEmailAddress expand through their own instantiations (SUBM = true: zk_expand3_subm,
+// CEA = true: zk_expand3_cea; the host expansion knows both)
+#define ZK_FOR_SEG_TYPES_ALL(X) ZK_FOR_SEG_TYPES(X) X(ZSEG_SUBM, ZkDecSubm) X(ZSEG_CEA, ZkDecCea)
 
 // one slot of any segment (pieces that straddle segments, the numbered-circuit expansion and the linear-row kernels
 // reach slots one by one)
-template <bool SUBM = false>
+template <bool SUBM = false, bool CEA = false>
 ZK_DEC inline u32 zk_decode_any(const ZkSeg& sg, u32 r, const ZkCtx& cx) {
   if constexpr (SUBM) { if (sg.type == ZSEG_SUBM) return ZkDecSubm(sg, cx)(r); }
+  if constexpr (CEA) { if (sg.type == ZSEG_CEA) return ZkDecCea(sg, cx)(r); }
   switch (sg.type) {
 #define ZK_X(T, D) case T: return D(sg, cx)(r);
     ZK_FOR_SEG_TYPES(ZK_X)
@@ -368,11 +400,19 @@ ZK_DEC inline u32 zk_decode_any(const ZkSeg& sg, u32 r, const ZkCtx& cx) {
 }
 // K slots r0 + i0, r0 + i0 + 64, ... of ONE segment (slots at or beyond `n` give 0): the type switch is taken once and the
 // K decodes are straight-line code, so their image reads are in flight together
-template <int K, bool SUBM = false>
+template <int K, bool SUBM = false, bool CEA = false>
 __device__ __forceinline__ void zk_decode_k(const ZkSeg& sg, u32 r0, u32 i0, u32 n, const ZkCtx& cx, u32 (&code)[K]) {
   if constexpr (SUBM) {
     if (sg.type == ZSEG_SUBM) {
       const ZkDecSubm dec(sg, cx);
+#pragma unroll
+      for (int k = 0; k < K; ++k) { const u32 i = i0 + 64u * (u32)k; code[k] = i < n ? dec(r0 + i) : 0u; }
+      return;
+    }
+  }
+  if constexpr (CEA) {
+    if (sg.type == ZSEG_CEA) {
+      const ZkDecCea dec(sg, cx);
 #pragma unroll
       for (int k = 0; k < K; ++k) { const u32 i = i0 + 64u * (u32)k; code[k] = i < n ? dec(r0 + i) : 0u; }
       return;

@@ -6,6 +6,7 @@
 #pragma once
 #include <hip/hip_runtime.h>
 #include <string.h>
+#include <algorithm>
 #include <mutex>
 #include <string>
 #include <vector>
@@ -14,7 +15,7 @@
 #include "zkwg_net_core.h"
 #include "zkwg_o0.h"
 
-#define ZK_MAX_KERNELS 9   // (EmailReveal: the five EmailVerifier roles + zk_substr + zk_app_tail + zk_expand = 8)
+#define ZK_MAX_KERNELS 9   // (EmailReveal: the five EmailVerifier roles + zk_substr + zk_app_tail + zk_expand = 8; CleanEmailAddress: 5 + 2 + 1)
 #define ZK_RS_SLOTS 16
 #define ZK_EV_RING 512     // launches whose HIP events are kept for zkwg_timing_summary
 
@@ -116,9 +117,9 @@ struct ZkTablesPart {
   u32 n_ent = 0;
   Fr* d_pos = nullptr;      // Poseidon(9): sparse-round table (zk_build_poseidon_sparse(10, 60)), dense tables, Montgomery constants, Poseidon(1)
   u32 pos_dense_off = 0, pos1_off = 0;
-  Fr* d_pos_rs = nullptr;   // removeSoftLineBreaks: Poseidon(16) then Poseidon(2) sparse-round tables
+  Fr* d_pos_rs = nullptr;   // removeSoftLineBreaks / CleanEmailAddress (PoseidonModular): Poseidon(16) then Poseidon(2) sparse-round tables
   u32 pos2_off = 0;
-  u32* d_pos_l29 = nullptr; // removeSoftLineBreaks: the same two tables in 29-bit limb form (zkwg_poseidon29.h)
+  u32* d_pos_l29 = nullptr; // the same two tables in 29-bit limb form (zkwg_poseidon29.h): zk_rslb_chunks / _merge1, zk_cea_chunks / _tail
   u32 pos2_l29_off = 0;
   Fr* d_rs_zero = nullptr;  // removeSoftLineBreaks: signals + digest of the all-zero chunk (constant chunks, zkwg_kernels_rslb.hip); null: off
   // fused Montgomery output, built on first use and published as a pair: v * R mod r for v < 65536 | the inverse table in Montgomery form
@@ -244,8 +245,9 @@ extern "C" void zk_set_last_error(const char* m);      // zkwg_api.hip: the thre
 static inline u64 out_W(const zkwg_circuit* c) { return c->lay.full_W ? c->lay.full_W : c->lay.s.W; }   // witness length the caller sees
 static inline u64 align256(u64 x) { return (x + 255) & ~255ull; }
 
-// scratch buffer of an n-email batch: [SHA chaining states | bits | small | fr (+256) | removeSoftLineBreaks: zk_rslb_chunks' dense-mix
-// staging, 153 words per 16-byte chunk, word-major (zkwg_poseidon29.h) | its two unit lists + counters | Montgomery copies (fr + limbs)].
+// scratch buffer of an n-email batch: [SHA chaining states | bits | small | fr (+256) | removeSoftLineBreaks / CleanEmailAddress: the chunk
+// kernel's dense-mix staging, 153 words per 16-element chunk, word-major (zkwg_poseidon29.h) | removeSoftLineBreaks: its two unit lists +
+// counters | Montgomery copies (fr + limbs)].
 // The Montgomery copies come LAST (round 6): a caller that never asks this buffer for a Montgomery-form output allocates
 // zkwg_scratch_bytes_standard -- half the bytes where the image is mostly field elements (removeSoftLineBreaks: 22 instead of 45 GB per
 // 4,096 emails, i.e. twice as many prepared batches in flight in the same HBM).
@@ -258,7 +260,9 @@ static inline ZkScratchLayout scratch_layout(const ZkSched& s, u64 n) {
   L.off_small = off; off += align256(n * (u64)s.img_small * 4);
   L.off_fr = off; off += align256(n * (u64)s.img_fr * 32) + 256;
   L.off_img_end = off;
-  L.rs_units = s.rslb ? (n * (u64)s.rs_nch + 63) / 64 * 64 : 0;
+  // (sized by the larger PoseidonModular of the circuit: chunk kernels follow each other on the caller's stream and may share the words)
+  const u64 nch = std::max(s.rslb ? s.rs_nch : 0u, s.cea.present ? s.cea.nch : 0u);
+  L.rs_units = (n * nch + 63) / 64 * 64;
   L.off_rs_stage = off; off += align256(L.rs_units * 153 * 4);
   L.off_rs_list = off; off += s.rslb ? align256(L.rs_units * 2 * 4) + 256 : 0;      // constant chunks: two unit lists | their two counters
   L.total_std = off;

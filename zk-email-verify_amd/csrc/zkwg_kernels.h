@@ -10,6 +10,8 @@ __global__ void zk_rsa(ZkSched s, ZkBufs B);         // zkwg_kernels_rsa.hip
 __global__ void zk_fpmul_small(ZkSched s, ZkBufs B);
 __global__ void zk_substr(ZkSched s, ZkBufs B);      // zkwg_kernels_substr.hip
 __global__ void zk_app_tail(ZkSched s, ZkBufs B);    // zkwg_kernels_app.hip
+__global__ void zk_cea_chunks(ZkSched s, ZkBufs B);  // zkwg_kernels_cea.hip (evaluator: zkwg_poseidon29.h, V = 6)
+__global__ void zk_cea_tail(ZkSched s, ZkBufs B);
 __global__ void zk_poseidon9(ZkSched s, ZkBufs B);   // zkwg_kernels_rsa.hip
 __global__ void zk_poseidon9_wave(ZkSched s, ZkBufs B);
 __global__ void zk_poseidon9_g16(ZkSched s, ZkBufs B);
@@ -33,6 +35,7 @@ __global__ void zk_expand3(ZkX3 A); __global__ void zk_expand3_mont(ZkX3 A);
 __global__ void zk_expand3_o0(ZkX3 A, ZkO0Dev O); __global__ void zk_expand3_o0_mont(ZkX3 A, ZkO0Dev O);
 __global__ void zk_image_to_mont(ZkX3 A);
 __global__ void zk_expand3_subm(ZkX3 A);             // zkwg_kernels_substr.hip: zk_expand3 with the ZSEG_SUBM decoder (substring mains)
+__global__ void zk_expand3_cea(ZkX3 A);              // zkwg_kernels_cea.hip: zk_expand3 with the ZSEG_CEA decoder (CleanEmailAddress)
 __global__ void zk_o0_rows_small(ZkX3 A, ZkO0Dev O);
 __global__ void zk_o0_chains_small(ZkX3 A, ZkO0Dev O);
 __global__ void zk_o0_generic(ZkX3 A, ZkO0Dev O);

@@ -284,6 +284,13 @@ int zkwg_prepare_device(zkwg_circuit_t* c, const void* d_in, uint64_t n, void* d
       return ZKWG_RC_OK;
     }
   }
+  if (s.cea.present) {
+    // CleanEmailAddress: chunk hashes (one lane per 16 elements of encoded || decoded), then per email the merges, chains and inversion
+    if (tm) hipEventRecord(evs[++ki], st);
+    if (pm & 64u) hipLaunchKernelGGL(zk_cea_chunks, dim3((u32)(((u64)ne * s.cea.nch + 63) / 64)), dim3(64), 0, st, s, B);
+    if (tm) hipEventRecord(evs[++ki], st);
+    if (pm & 128u) hipLaunchKernelGGL(zk_cea_tail, dim3((ne + 63) / 64), dim3(64), 0, st, s, B);
+  }
   if (!(s.rslb && !c->rs.sync) && (pm & 256u)) {   // (timed with the last prepare kernel)
     if (c->lay.full_W) launch_o0_rows(c, c->o0.d, B, st);
     if (c->abc.m) launch_o0_rows(c, c->abc.d, B, st);
@@ -300,7 +307,7 @@ static int expand_impl(zkwg_circuit_t* c, const void* d_in, uint64_t n, const vo
   if (count == 0) return ZKWG_RC_OK;
   const ZkSched& s = c->lay.s;
   if (abc && !c->abc.m) return ZKWG_RC_BAD_CONFIG;
-  if (mont && s.sub.present) return ZKWG_RC_BAD_CONFIG;   // substring mains and EmailReveal: no Montgomery-form output
+  if (mont && (s.sub.present || s.cea.present)) return ZKWG_RC_BAD_CONFIG;   // substring mains, EmailReveal, CleanEmailAddress: no Montgomery-form output
   // the descriptor table written from: the attached system's A.w | B.w | C.w, a numbered circuit's wires, or none (kept-v1 pieces)
   const ZkO0Dev* OD = abc ? &c->abc.d : (c->lay.full_W ? &c->o0.d : nullptr);
   if (first + count > n || out_stride < (abc ? 3 * c->abc.m : out_W(c)) * 32 || (out_stride & 15)) return ZKWG_RC_BAD_ARG;
@@ -365,6 +372,7 @@ static int expand_impl(zkwg_circuit_t* c, const void* d_in, uint64_t n, const vo
       const dim3 g3((u32)units3), b3(256);
       // (mont was refused above) EmailReveal without the uniqueness check has no match matrix: the plain kernel serves
       if (s.app.present ? s.sub.uniq != 0 : s.sub.present != 0) hipLaunchKernelGGL(zk_expand3_subm, g3, b3, 0, st, A);
+      else if (s.cea.present) hipLaunchKernelGGL(zk_expand3_cea, g3, b3, 0, st, A);
       else hipLaunchKernelGGL(mont ? zk_expand3_mont : zk_expand3, g3, b3, 0, st, A);
     }
   }

@@ -566,6 +566,82 @@ static inline void zk_walk_rslb(ZkWalker& w, const std::string& p, const ZkSched
   w.one(p + ".anon_IsEqual_final.isz.out"); w.one(p + ".anon_IsEqual_final.isz.inv");
 }
 
+// ------------------------------------------------------------------ CleanEmailAddress
+// utils/email.circom:16-140 as the component `p`, over encoded[] / decoded[] at the record offsets in_enc / in_dec.  Kept: the
+// quadratic intermediates in declaration order (:22-40), rHasher's S-boxes, the IsZero pairs of the IsEqual call sites, muxEnc's
+// products, the final IsEqual.  r, isPlus, isAt, isPeriod, foundPlus, hasAliasPart, inAliasPartTemp, shouldRemove, rEnc and the
+// first element of isLocalPart, afterPlus, afterAt, rDec are linear: dropped.  The six anonymous IsEqual call sites (:55, :56, :60,
+// :61, :68, :139) are named anon_IsEqual_plus0 / _at0 / _plus / _at / _period / _final.
+static inline void zk_alloc_cea(ZkWalker& w, ZkCeaLayout& E, u32 L, u32 in_enc, u32 in_dec) {
+  E.present = 1; E.L = L; E.nch = L / 8; E.in_enc = in_enc; E.in_dec = in_dec;
+  E.m_pos = w.alloc_small(2);
+  E.f_chunk = w.alloc_fr(E.nch + 1);
+  E.f_rdec = w.alloc_fr(L - 1);
+  E.f_sum_enc = w.alloc_fr(L);
+  E.f_sum_dec = w.alloc_fr(L);
+  E.f_hash = w.alloc_fr(E.nch * ZK_P16_KEPT + (E.nch - 1) * ZK_P2_KEPT);
+  E.f_mux = w.alloc_fr(2 * L - 1);
+  E.f_final = w.alloc_fr(2);
+}
+static inline void zk_walk_cea(ZkWalker& w, const std::string& p, const ZkCeaLayout& E) {
+  const u32 L = E.L, enc = E.in_enc;
+  auto bytes = [&](u32 kind, u32 i0, const char* nm) {
+    w.seg(ZSEG_CEA, L - i0, enc, kind | (i0 << 8), E.m_pos, L);
+    if (!w.names) w.skip(L - i0); else for (u32 i = i0; i < L; ++i) w.one(zk_idx(p + nm, i));
+  };
+  bytes(ZCEA_PAA, 0, ".isPlusAndAt");
+  bytes(ZCEA_LOCAL, 1, ".isLocalPart");
+  bytes(ZCEA_LPER, 0, ".isLocalPeriod");
+  bytes(ZCEA_APLUS, 1, ".afterPlus");
+  bytes(ZCEA_AAT, 1, ".afterAt");
+  bytes(ZCEA_ALIAS, 0, ".inAliasPart");
+  bytes(ZCEA_PROC, 0, ".processed");
+  w.seg(ZSEG_FR, L - 1, E.f_rdec);
+  if (!w.names) w.skip(L - 1); else for (u32 i = 1; i < L; ++i) w.one(zk_idx(p + ".rDec", i));
+  w.seg(ZSEG_FR, L, E.f_sum_enc); w.arr(p + ".sumEnc", L);
+  w.seg(ZSEG_FR, L, E.f_sum_dec); w.arr(p + ".sumDec", L);
+  // rHasher = PoseidonModular(2 L): Poseidon(16) per chunk, Poseidon(2) merges (the names zk_walk_rslb gives the same template)
+  w.seg(ZSEG_FR, E.nch * ZK_P16_KEPT + (E.nch - 1) * ZK_P2_KEPT, E.f_hash);
+  for (u32 c = 0; c < E.nch; ++c) {
+    zk_walk_poseidon_names(w, zk_idx(p + ".rHasher.anon_Poseidon_chunk", c), 17, 68);
+    if (c) zk_walk_poseidon_names(w, zk_idx(p + ".rHasher.anon_Poseidon_merge", c), 3, 57);
+  }
+  // IsEqual()([encoded[i], 43]) and ([encoded[i], 64]): position 0 has call sites of its own, the loop's instances count from 0 (:55-64)
+  w.seg(ZSEG_CEA, 4 * L, enc, ZCEA_EQ2, E.m_pos, L);
+  if (!w.names) w.skip(4 * L);
+  else for (u32 i = 0; i < L; ++i)
+    for (const char* nm : {".anon_IsEqual_plus", ".anon_IsEqual_at"}) {
+      const std::string q = i ? zk_idx(p + nm, i - 1) : p + nm + "0";
+      w.one(q + ".isz.out"); w.one(q + ".isz.inv");
+    }
+  w.seg(ZSEG_CEA, 2 * L, enc, ZCEA_EQP, E.m_pos, L);
+  if (!w.names) w.skip(2 * L);
+  else for (u32 i = 0; i < L; ++i) { w.one(zk_idx(p + ".anon_IsEqual_period", i) + ".isz.out"); w.one(zk_idx(p + ".anon_IsEqual_period", i) + ".isz.inv"); }
+  // muxEnc[i] = Mux1 -> MultiMux1(1): c[0] is fed a product for i >= 1 (:114); mux.out[0] is quadratic
+  w.seg(ZSEG_FR, 2 * L - 1, E.f_mux);
+  if (!w.names) w.skip(2 * L - 1);
+  else for (u32 i = 0; i < L; ++i) {
+    if (i) w.one(zk_idx(p + ".muxEnc", i) + ".c[0]");
+    w.one(zk_idx(p + ".muxEnc", i) + ".mux.out[0]");
+  }
+  w.seg(ZSEG_FR, 2, E.f_final);
+  w.one(p + ".anon_IsEqual_final.isz.out"); w.one(p + ".anon_IsEqual_final.isz.inv");
+}
+// main = CleanEmailAddress(L), no public inputs (tests/test-circuits/clean-email-address-test.circom:5: (32))
+static inline void zk_walk_main_cea(ZkWalker& w, ZkSched& s, u32 L) {
+  ZkCeaLayout& E = s.cea;
+  s.m_one = w.alloc_small(1);
+  E.m_valid = w.alloc_small(1);                  // (m_one and m_valid are consecutive)
+  zk_alloc_cea(w, E, L, s.in_off[0], s.in_off[1]);
+  w.seg(ZSEG_SMALL, 2, s.m_one);
+  w.one("one");
+  w.one("main.isValid");
+  w.seg(ZSEG_IN8, L, E.in_enc); w.arr("main.encoded", L);
+  w.seg(ZSEG_IN8, L, E.in_dec); w.arr("main.decoded", L);
+  zk_walk_cea(w, "main", E);
+  s.n_public = 1;   // the output only
+}
+
 // ------------------------------------------------------------------ EmailVerifier main
 // (packages/circuits/email-verifier.circom:42-174, flags (ignoreBodyHashCheck, 0, 0, 0),
 //  `component main { public [ pubkey ] }`, tests/test-circuits/email-verifier-test.circom:5)

@@ -65,7 +65,23 @@ enum ZkSegType : u32 {
   // which exist only for a handle with a descriptor consumer (zkwg_o0.h) -- the public segment table reports those four types
   ZSEG_SHAR_SP = 24, ZSEG_SHAR_T1 = 25, ZSEG_SHAR_T2 = 26,
   ZSEG_SHAR_SUM = 27,  // suma[64], sume[64], fsum[8]: 136 x 33 slots
-  ZSEG_NTYPES = 28
+  ZSEG_CEA = 28,    // CleanEmailAddress byte-derived arrays over encoded[] = in[src ..] (utils/email.circom:55-103): a = ZkCeaKind | first index << 8,
+                    // b = small index of (first '+', first '@'), c = maxLength (decoded by ZkDecCea, which only zk_expand3_cea and the host
+                    // expansion instantiate: zkwg_kernels_cea.hip)
+  ZSEG_NTYPES = 29
+};
+
+// ZSEG_CEA kinds; i = r + the segment's first index, P / A = index of the first '+' / '@' in encoded[] (maxLength: none)
+enum ZkCeaKind : u32 {
+  ZCEA_PAA = 0,    // isPlusAndAt[i] = (1 - isPlus[i]) (1 - isAt[i])
+  ZCEA_LOCAL = 1,  // isLocalPart[i] = i < min(P, A)
+  ZCEA_LPER = 2,   // isLocalPeriod[i] = isLocalPart[i] (encoded[i] == '.')
+  ZCEA_APLUS = 3,  // afterPlus[i] = i < P
+  ZCEA_AAT = 4,    // afterAt[i] = i < A
+  ZCEA_ALIAS = 5,  // inAliasPart[i] = hasAliasPart (afterAt[i] - afterPlus[i]): -1 on A <= i < P
+  ZCEA_PROC = 6,   // processed[i] = (1 - shouldRemove[i]) encoded[i], shouldRemove = isLocalPeriod + inAliasPart in {-1, 0, 1}
+  ZCEA_EQ2 = 7,    // per position 4 slots: IsEqual([encoded[i], 43]) (isz.out, isz.inv), IsEqual([encoded[i], 64]) (isz.out, isz.inv)
+  ZCEA_EQP = 8     // per position 2 slots: IsEqual([encoded[i], 46]) (isz.out, isz.inv)
 };
 
 // ZSEG_RSLB kinds (helpers/remove-soft-line-breaks.circom:14-126); enc = the emailBody bytes at src
@@ -109,6 +125,7 @@ ZK_HD bool zk_seg_is_immediate(const ZkSeg& g) {
     case ZSEG_SHAR_SP: case ZSEG_SHAR_T1: case ZSEG_SHAR_T2: case ZSEG_SHAR_SUM: return true;
     case ZSEG_DFA: return g.a != ZDFA_EQ;
     case ZSEG_RSLB: return g.a != ZRS_EQ;
+    case ZSEG_CEA: return (g.a & 0xffu) != ZCEA_ALIAS && (g.a & 0xffu) < ZCEA_EQ2;
     default: return false;
   }
 }
@@ -217,6 +234,22 @@ struct ZkAppLayout {
   u32 f_out;             // fr: (nullifier) emailNullifier, then revealed[chunks]
   u32 f_pos;             // fr: (nullifier) 420 S-box signals of Poseidon(9), then 216 of Poseidon(1)
 };
+// CleanEmailAddress(L) (utils/email.circom:16-140; zkwg_cea_core.h): the main of clean-email-address-test.circom, or a component
+// of a later application main (zkwg_layout.h zk_alloc_cea / zk_walk_cea take the path prefix and the record offsets)
+struct ZkCeaLayout {
+  u32 present;           // 1: the block is part of the circuit
+  u32 L, nch;            // maxLength (a multiple of 8), L / 8 Poseidon(16) chunks of PoseidonModular(2 L)
+  u32 in_enc, in_dec;    // record offsets of encoded[L], decoded[L]
+  u32 m_valid;           // small: isValid (the main: follows m_one)
+  u32 m_pos;             // small: index of the first '+', of the first '@' in encoded[] (L: none)
+  u32 f_chunk;           // fr: nch chunk digests, then r (not part of the witness)
+  u32 f_rdec;            // fr: rDec[1 .. L)
+  u32 f_sum_enc;         // fr: sumEnc[L]
+  u32 f_sum_dec;         // fr: sumDec[L]
+  u32 f_hash;            // fr: rHasher S-box signals, chunk c at zk_rs_chunk_off(c), its merge at +612
+  u32 f_mux;             // fr: muxEnc: mux[0].out, then (c[0], mux.out) for i = 1 .. L-1
+  u32 f_final;           // fr: final IsEqual (isz.out, isz.inv)
+};
 #define ZK_APP_PACK 31u       // MAX_BYTES_IN_FIELD (utils/constants.circom)
 #define ZK_P9_KEPT 420u       // Poseidon(9):  3 * (8 * 10 + 60)
 #define ZK_P1_KEPT 216u       // Poseidon(1):  3 * (8 * 2 + 56)
@@ -262,6 +295,7 @@ struct ZkSched {
   ZkFpgLayout fpg;       // main = FpMul(n, k) with small parameters
   ZkSubLayout sub;       // main = RevealSubstring / CountSubstringOccurrences; EmailReveal: its RevealSubstring component
   ZkAppLayout app;       // main = EmailReveal
+  ZkCeaLayout cea;       // main = CleanEmailAddress
   // EmailVerifier main (email-verifier.circom:42-174)
   u32 f_out;             // fr: pubkeyHash, shaHi, shaLo
   u32 f_pos;             // fr: 420 Poseidon S-box signals

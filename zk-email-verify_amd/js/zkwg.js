@@ -22,6 +22,8 @@ const MAIN_EMAIL_VERIFIER = 0, MAIN_SHA256_BYTES = 1, MAIN_RSA_VERIFIER = 2, MAI
 const MAIN_REVEAL_SUBSTRING = 4, MAIN_COUNT_SUBSTRING = 5;
 // EmailReveal(maxHeader, maxBody, n, k, ignoreBodyHashCheck, revealFromBody, maxSubstring, checkUniqueness, withNullifier): circuits/email-reveal.circom
 const MAIN_EMAIL_REVEAL = 6;
+// CleanEmailAddress(maxHeader) with maxBody = maxHeader, a multiple of 8 in [8, 1024], n = k = 0: utils/email.circom:16-140
+const MAIN_CLEAN_EMAIL_ADDRESS = 7;
 const IN = { HEADER: 0, BODY: 1, PRECOMPUTED_SHA: 2, PUBKEY: 3, SIGNATURE: 4, MESSAGE: 5, HEADER_LEN: 6, BODY_LEN: 7, BODY_HASH_INDEX: 8, HEADER_MASK: 9, BODY_MASK: 10, DECODED_BODY: 11, RANGE_FLAGS: 12, SUBSTRING_START: 13, SUBSTRING_LEN: 14 };
 
 function norm(v) {
@@ -73,6 +75,7 @@ class Circuit {
     if (o.mainKind === MAIN_FP_MUL) return { a: o.k, b: o.k, p: o.k };   // FpMul(n, k) (tests/test-circuits/fp-mul-test.circom)
     if (o.mainKind === MAIN_REVEAL_SUBSTRING) return { in: o.maxHeader, substringStartIndex: 1, substringLength: 1 };
     if (o.mainKind === MAIN_COUNT_SUBSTRING) return { in: o.maxHeader, substring: o.maxBody };
+    if (o.mainKind === MAIN_CLEAN_EMAIL_ADDRESS) return { encoded: o.maxHeader, decoded: o.maxHeader };
     const s = { emailHeader: o.maxHeader, emailHeaderLength: 1, pubkey: o.k, signature: o.k };
     if (o.enableHeaderMasking) s.headerMask = o.maxHeader;
     if (!o.ignoreBodyHashCheck) {
@@ -142,6 +145,12 @@ class Circuit {
       bytes(IN.HEADER, flat.in, 'in');
       if (o.mainKind === MAIN_COUNT_SUBSTRING) bytes(IN.BODY, flat.substring, 'substring');
       else { u32(IN.BODY_HASH_INDEX, flat.substringStartIndex[0], 'substringStartIndex'); u32(IN.BODY_LEN, flat.substringLength[0], 'substringLength'); }
+    } else if (o.mainKind === MAIN_CLEAN_EMAIL_ADDRESS) {
+      // the template asserts nothing: a value that is not a byte would have a witness this path cannot form, so it is refused here
+      for (const key of ['encoded', 'decoded']) {
+        if (flat[key].some((v) => v > 255n)) throw new Error('input signal ' + key + ' holds a value that is not a byte');
+      }
+      bytes(IN.HEADER, flat.encoded, 'encoded'); bytes(IN.BODY, flat.decoded, 'decoded');
     } else {
       bytes(IN.HEADER, flat.emailHeader, 'emailHeader'); u32(IN.HEADER_LEN, flat.emailHeaderLength[0], 'emailHeaderLength');
       limbs(IN.PUBKEY, flat.pubkey, 'pubkey'); limbs(IN.SIGNATURE, flat.signature, 'signature');
@@ -428,4 +437,4 @@ function symbols(circuit) {
 }
 
 module.exports = { symbols, R1cs, Circuit, WitnessCalculator, MultiCalculator, Prover, Tester, tester, wtns, groth16, FIELD_MODULUS, MAIN_EMAIL_VERIFIER, MAIN_SHA256_BYTES, MAIN_RSA_VERIFIER, MAIN_FP_MUL,
-  MAIN_REVEAL_SUBSTRING, MAIN_COUNT_SUBSTRING, MAIN_EMAIL_REVEAL };
+  MAIN_REVEAL_SUBSTRING, MAIN_COUNT_SUBSTRING, MAIN_EMAIL_REVEAL, MAIN_CLEAN_EMAIL_ADDRESS };

@@ -15,7 +15,7 @@ import ctypes as C
 
 from . import _lib
 from ._lib import (Config, MAIN_EMAIL_VERIFIER, MAIN_SHA256_BYTES, MAIN_RSA_VERIFIER, MAIN_FP_MUL, MAIN_REVEAL_SUBSTRING,
-                   MAIN_COUNT_SUBSTRING, MAIN_EMAIL_REVEAL)
+                   MAIN_COUNT_SUBSTRING, MAIN_EMAIL_REVEAL, MAIN_CLEAN_EMAIL_ADDRESS)
 
 FIELD_MODULUS = 21888242871839275222246405745257275088548364400416034343698204186575808495617
 
@@ -50,7 +50,9 @@ _FIELD_OF = {"emailHeader": 0, "paddedIn": 0, "emailBody": 1, "precomputedSHA": 
              "signature": 4, "b": 4, "message": 5, "p": 5, "emailHeaderLength": 6, "paddedInLength": 6, "emailBodyLength": 7,
              "bodyHashIndex": 8, "headerMask": 9, "bodyMask": 10, "decodedEmailBodyIn": 11,
              # RevealSubstring / CountSubstringOccurrences (helpers/reveal-substring.circom:16-18, utils/array.circom:229-230)
-             "in": 0, "substring": 1, "substringLength": 7, "substringStartIndex": 8}
+             "in": 0, "substring": 1, "substringLength": 7, "substringStartIndex": 8,
+             # CleanEmailAddress (utils/email.circom:17-18)
+             "encoded": 0, "decoded": 1}
 # EmailReveal (circuits/email-reveal.circom): the two indices have record fields of their own (7 and 8 hold EmailVerifier's)
 _FIELD_OF_APP = dict(_FIELD_OF, substringStartIndex=13, substringLength=14)
 
@@ -144,6 +146,8 @@ class Circuit:
             return {"in": c.max_header, "substringStartIndex": 1, "substringLength": 1}
         if c.main_kind == MAIN_COUNT_SUBSTRING:
             return {"in": c.max_header, "substring": c.max_body}
+        if c.main_kind == MAIN_CLEAN_EMAIL_ADDRESS:
+            return {"encoded": c.max_header, "decoded": c.max_header}
         sizes = {"emailHeader": c.max_header, "emailHeaderLength": 1, "pubkey": c.k, "signature": c.k}
         if c.enable_header_masking:
             sizes["headerMask"] = c.max_header
@@ -223,6 +227,12 @@ class Circuit:
             else:
                 bhi = as_u32(flat["substringStartIndex"][0], "substringStartIndex")
                 blen = as_u32(flat["substringLength"][0], "substringLength")
+        elif c.main_kind == MAIN_CLEAN_EMAIL_ADDRESS:
+            # the template asserts nothing, so a value that is not a byte would have a witness this path cannot form: refused here
+            for key in ("encoded", "decoded"):
+                if any(v > 255 for v in flat[key]):
+                    raise ZkwgError(f"input signal {key} holds a value that is not a byte")
+            header, body = bytes(flat["encoded"]), bytes(flat["decoded"])
         else:
             header = as_bytes(flat["emailHeader"], "emailHeader")
             hlen = as_u32(flat["emailHeaderLength"][0], "emailHeaderLength")
@@ -772,6 +782,8 @@ class WitnessCalculator:
             elif cfg.main_kind == MAIN_COUNT_SUBSTRING:
                 data = zr.write_r1cs(len(sym), zr.count_substring_main_constraints(sym, cfg.max_header, cfg.max_body),
                                      1, 0, cfg.max_header + cfg.max_body)
+            elif cfg.main_kind == MAIN_CLEAN_EMAIL_ADDRESS:
+                data = zr.write_r1cs(len(sym), zr.clean_email_address_main_constraints(sym, cfg.max_header), 1, 0, 2 * cfg.max_header)
             elif cfg.main_kind == MAIN_EMAIL_REVEAL:
                 a = c.app
                 data = zr.email_reveal_r1cs(sym, cfg.max_header, cfg.max_body, cfg.ignore_body_hash_check, a.reveal_from_body,

@@ -72,6 +72,7 @@ DKIM_SKIP_BODY_HASH = 1
 
 MAIN_EMAIL_VERIFIER, MAIN_SHA256_BYTES, MAIN_RSA_VERIFIER, MAIN_FP_MUL = 0, 1, 2, 3
 MAIN_REVEAL_SUBSTRING, MAIN_COUNT_SUBSTRING = 4, 5   # RevealSubstring(L, S, uniq), CountSubstringOccurrences(L, S): max_header = L, max_body = S, n = uniq
+MAIN_CLEAN_EMAIL_ADDRESS = 7   # CleanEmailAddress(L) (utils/email.circom): max_header = max_body = L, a multiple of 8 in [8, 1024], n = k = 0
 MAIN_EMAIL_REVEAL = 6   # EmailReveal(...): EmailVerifier + RevealSubstring + PackBytes + EmailNullifier (zkwg_circuit_create_app)
 (IN_HEADER, IN_BODY, IN_PRECOMPUTED_SHA, IN_PUBKEY, IN_SIGNATURE, IN_MESSAGE,
  IN_HEADER_LEN, IN_BODY_LEN, IN_BODY_HASH_INDEX, IN_HEADER_MASK, IN_BODY_MASK, IN_DECODED_BODY,

@@ -1,7 +1,7 @@
 """`python -m zkwg.generate_witness <circuit> <input.json> <witness.wtns> [device]` -- counterpart of circom's
 generated `generate_witness.js` as the reference documents it (docs/zk-email-docs/UsageGuide/README.md:132-140:
 `node generate_witness.js circuit.wasm input.json witness.wtns`).  <circuit> names the circuit by its template
-parameters instead of a WASM file: `EmailVerifier(1024,1536,121,17,0,0,0,0)` or a JSON object / file with the
+parameters instead of a WASM file: `EmailVerifier(1024,1536,121,17,0,0,0,0)`, `CleanEmailAddress(32)` or a JSON object / file with the
 keyword arguments of zkwg.Circuit.  An input file holding a list writes <witness>_<i>.wtns per email and exits 1
 if any email failed.  `--eml`: <input> is a raw email; it is verified first (zkwg.dkim, keys from `--keys keys.json`:
 name -> TXT records) and its inputs are generated for the circuit's sizes (zkwg.inputs.generate_email_verifier_inputs)."""
@@ -28,6 +28,9 @@ def circuit_kwargs(arg):
     m = re.fullmatch(r"\s*CountSubstringOccurrences\(\s*(\d+)\s*,\s*(\d+)\s*\)\s*", arg)
     if m:   # utils/array.circom:226
         return dict(main_kind=zkwg.MAIN_COUNT_SUBSTRING, max_header=int(m.group(1)), max_body=int(m.group(2)), n=0, k=0)
+    m = re.fullmatch(r"\s*CleanEmailAddress\(\s*(\d+)\s*\)\s*", arg)
+    if m:   # utils/email.circom:16
+        return dict(main_kind=zkwg.MAIN_CLEAN_EMAIL_ADDRESS, max_header=int(m.group(1)), max_body=int(m.group(1)), n=0, k=0)
     m = re.fullmatch(r"\s*EmailReveal\(([\d\s,]+)\)\s*", arg)
     if m:   # circuits/email-reveal.circom
         p = [int(x) for x in m.group(1).split(",")]

@@ -252,3 +252,25 @@ def generate_email_reveal_inputs(raw_eml, params=None, keys=None, needle=None, s
     a = dict(dkim_verification_args or {})
     result = dkim.verify_dkim_signature(raw_eml, a.get("domain") or "", a.get("enableSanitization", True), keys=keys, device=device)
     return generate_email_reveal_inputs_from_dkim_result(result, params, needle, start, length)
+
+
+def clean_email_address(addr):
+    """The address CleanEmailAddress (utils/email.circom:16-140) accepts as `decoded` for `encoded` = addr: the periods of the
+    local part and the "+alias" up to the '@' removed ("a.b+c@d.e" -> "ab@d.e").  The template means exactly one '@' with no
+    '+' behind it; anything else has a witness too, but not this meaning: ValueError."""
+    if addr.count("@") != 1:
+        raise ValueError("the address needs exactly one '@'")
+    local, domain = addr.split("@")
+    if "+" in domain:
+        raise ValueError("a '+' behind the '@' is outside what the template means")
+    return local.split("+")[0].replace(".", "") + "@" + domain
+
+
+def generate_clean_email_address_inputs(addr, max_length):
+    """The CircuitInput of CleanEmailAddress(max_length) for an address: encoded = its bytes, decoded = those of
+    clean_email_address(addr), both zero-padded to max_length."""
+    enc, dec = addr.encode("ascii"), clean_email_address(addr).encode("ascii")
+    if len(enc) > max_length:
+        raise ValueError(f"the address is longer than max_length = {max_length}")
+    pad = lambda b: [str(v) for v in b] + ["0"] * (max_length - len(b))
+    return {"encoded": pad(enc), "decoded": pad(dec)}

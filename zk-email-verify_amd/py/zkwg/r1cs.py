@@ -1022,6 +1022,84 @@ def remove_soft_line_breaks(g, pre, enc, dec):
     return g.iszero(pre + ".anon_IsEqual_final.isz", lc_add(wire(s_dec[M - 1]), wire(s_enc[M - 1]), -1))
 
 
+def clean_email_address(g, pre, enc, dec):
+    """CleanEmailAddress(L) (utils/email.circom:16-140) as the component `pre`; enc / dec: lists of byte wires.  Returns isValid as
+    a linear combination.  The dropped linear signals (r, isPlus, isAt, isPeriod, foundPlus, hasAliasPart, inAliasPartTemp,
+    shouldRemove, rEnc, the first elements of the running products) appear as linear combinations of kept wires."""
+    L = len(enc)
+    slot = g.slot
+    data = list(enc) + list(dec)
+    r = None
+    for c in range(len(data) // 16):      # r = PoseidonModular(2 L)(encoded || decoded) (utils/hash.circom:49-82)
+        h = poseidon_constraints(g.cons, slot, f"{pre}.rHasher.anon_Poseidon_chunk[{c}]", data[16 * c:16 * c + 16])
+        r = h if c == 0 else poseidon_constraints(g.cons, slot, f"{pre}.rHasher.anon_Poseidon_merge[{c}]", [r, h])
+    site = lambda nm, i: f"{pre}.anon_IsEqual_{nm}0.isz" if i == 0 else f"{pre}.anon_IsEqual_{nm}[{i - 1}].isz"
+    is_plus = [g.iszero(site("plus", i), lc_add(const(43), enc[i], -1)) for i in range(L)]
+    is_at = [g.iszero(site("at", i), lc_add(const(64), enc[i], -1)) for i in range(L)]
+    is_period = [g.iszero(f"{pre}.anon_IsEqual_period[{i}].isz", lc_add(const(46), enc[i], -1)) for i in range(L)]
+
+    def running(name, first, factor):     # x[0] = first (linear), x[i] <== x[i-1] * factor[i]
+        out = [first]
+        for i in range(1, L):
+            w_ = wire(slot[f"{pre}.{name}[{i}]"])
+            g.cons.append((out[-1], factor[i], w_))
+            out.append(w_)
+        return out
+    paa = [wire(s) for s in g.arr(pre + ".isPlusAndAt", L)]
+    for i in range(L):
+        g.cons.append((one_minus(is_plus[i]), one_minus(is_at[i]), paa[i]))
+    local = running("isLocalPart", paa[0], paa)
+    lper = [wire(s) for s in g.arr(pre + ".isLocalPeriod", L)]
+    for i in range(L):
+        g.cons.append((local[i], is_period[i], lper[i]))
+    after_plus = running("afterPlus", one_minus(is_plus[0]), [one_minus(x) for x in is_plus])
+    after_at = running("afterAt", one_minus(is_at[0]), [one_minus(x) for x in is_at])
+    has_alias = one_minus(after_plus[L - 1])
+    alias = [wire(s) for s in g.arr(pre + ".inAliasPart", L)]
+    proc = [wire(s) for s in g.arr(pre + ".processed", L)]
+    remove = []
+    for i in range(L):
+        g.cons.append((has_alias, lc_add(after_at[i], after_plus[i], -1), alias[i]))
+        remove.append(lc_add(lper[i], alias[i]))
+        g.cons.append((one_minus(remove[i]), enc[i], proc[i]))
+    # muxEnc[i] = Mux1 -> MultiMux1(1): out = (c[1] - c[0]) * s + c[0]
+    r_enc = []
+    for i in range(L):
+        if i == 0:
+            c0, c1 = r, const(1)
+        else:
+            c0 = wire(slot[f"{pre}.muxEnc[{i}].c[0]"])
+            g.cons.append((r_enc[i - 1], r, c0))
+            c1 = r_enc[i - 1]
+        o = wire(slot[f"{pre}.muxEnc[{i}].mux.out[0]"])
+        g.cons.append((lc_add(c1, c0, -1), remove[i], lc_add(o, c0, -1)))
+        r_enc.append(o)
+    r_dec = running("rDec", r, [r] * L)
+    s_enc, s_dec = g.arr(pre + ".sumEnc", L), g.arr(pre + ".sumDec", L)
+    for i in range(L):
+        g.cons.append((r_enc[i], proc[i], lc_add(wire(s_enc[i]), wire(s_enc[i - 1]) if i else {}, -1)))
+        g.cons.append((r_dec[i], dec[i], lc_add(wire(s_dec[i]), wire(s_dec[i - 1]) if i else {}, -1)))
+    return g.iszero(pre + ".anon_IsEqual_final.isz", lc_add(wire(s_dec[L - 1]), wire(s_enc[L - 1]), -1))
+
+
+def clean_email_address_constraint_count(L):
+    """constraints clean_email_address_main_constraints emits: 3 per S-box of the L / 8 Poseidon(16) and
+    L / 8 - 1 Poseidon(2), 2 per IsZero of the 3 L + 1 IsEqual, isPlusAndAt, isLocalPeriod, inAliasPart, processed, muxEnc's
+    mux.out, sumEnc, sumDec [L], isLocalPart, afterPlus, afterAt, muxEnc's c[0], rDec [L - 1], and the row of isValid"""
+    nch = L // 8
+    return 3 * (nch * (8 * 17 + 68) + (nch - 1) * (8 * 3 + 57)) + 2 * (3 * L + 1) + 7 * L + 5 * (L - 1) + 1
+
+
+def clean_email_address_main_constraints(symbols, L):
+    """`component main = CleanEmailAddress(L)` (tests/test-circuits/clean-email-address-test.circom:5: (32))"""
+    slot_of = {nm: s for s, nm in symbols}
+    g = RsaBuilder(slot_of, "main")
+    enc = [wire(slot_of[f"main.encoded[{i}]"]) for i in range(L)]
+    dec = [wire(slot_of[f"main.decoded[{i}]"]) for i in range(L)]
+    g.lin(lc_add(wire(slot_of["main.isValid"]), clean_email_address(g, "main", enc, dec), -1))
+    return g.cons
+
+
 def write_r1cs(n_wires, constraints, n_pub_out=0, n_pub_in=0, n_prv_in=0, header_last=False):
     """constraints: list of (A, B, C), each a dict wire -> coefficient (ints mod P)."""
     def lc(d):
@@ -1075,10 +1153,12 @@ def _main():
     import argparse
     import zkwg
     ap = argparse.ArgumentParser(description=__doc__.split("\n\n")[0])
-    ap.add_argument("--main", choices=["email-verifier", "sha256-bytes", "rsa-verifier", "reveal-substring", "count-substring", "email-reveal"],
+    ap.add_argument("--main", choices=["email-verifier", "sha256-bytes", "rsa-verifier", "reveal-substring", "count-substring", "email-reveal",
+                                       "clean-email-address"],
                     default="email-verifier",
                     help="main component (tests/test-circuits/{email-verifier,sha,rsa,reveal-substring,count-substring-occurrences}-test.circom)")
-    ap.add_argument("--max-length", type=int, default=256, help="reveal-substring / count-substring: maxLength / maxLen")
+    ap.add_argument("--max-length", type=int, default=256,
+                    help="reveal-substring / count-substring: maxLength / maxLen; clean-email-address: maxLength (a multiple of 8 up to 1024)")
     ap.add_argument("--max-substring", type=int, default=16, help="reveal-substring / count-substring: maxSubstringLength / maxSubstringLen")
     ap.add_argument("--check-uniqueness", type=int, default=1, choices=[0, 1], help="reveal-substring: shouldCheckUniqueness")
     ap.add_argument("--reveal-from-body", type=int, default=0, choices=[0, 1], help="email-reveal: revealFromBody")
@@ -1112,6 +1192,10 @@ def _main():
         sym = c.symbols()
         data = write_r1cs(len(sym), count_substring_main_constraints(sym, a.max_length, a.max_substring),
                           n_pub_out=1, n_pub_in=0, n_prv_in=a.max_length + a.max_substring)
+    elif a.main == "clean-email-address":
+        c = zkwg.Circuit(zkwg.MAIN_CLEAN_EMAIL_ADDRESS, max_header=a.max_length, max_body=a.max_length, n=0, k=0, device=-1)
+        sym = c.symbols()
+        data = write_r1cs(len(sym), clean_email_address_main_constraints(sym, a.max_length), n_pub_out=1, n_pub_in=0, n_prv_in=2 * a.max_length)
     elif a.main == "email-reveal":
         c = zkwg.Circuit(zkwg.MAIN_EMAIL_REVEAL, max_header=a.max_header, max_body=a.max_body, device=-1,
                          ignore_body_hash_check=a.ignore_body_hash_check, reveal_from_body=a.reveal_from_body,
