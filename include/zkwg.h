@@ -288,7 +288,9 @@ int zkwg_calculate_batch(zkwg_circuit_t* c, const uint8_t* packed_inputs, uint64
  * All pointers are device pointers; `selector` is the optional shaPrecomputeSelector (shared by the
  * batch).  d_records receives n packed input records (zkwg_input_stride each); d_gen_status[i]:
  *   0 ok | 1 header does not fit maxHeadersLength | 2 remaining body longer than maxBodyLength
- *   | 3 selector not found in the body | 4 body longer than body_stride.   EmailVerifier main only. */
+ *   | 3 selector not found in the body | 4 body longer than body_stride
+ *   | 5 needle absent | 6 needle not unique | 7 needle empty or too long (zkwg_generate_reveal_inputs_device only, below).
+ * EmailVerifier, and EmailReveal with its two index fields left zero for the caller. */
 typedef struct zkwg_dkim_batch {
   const uint8_t* headers;        /* [n][header_stride] canonical signed header bytes */
   const uint32_t* header_len;    /* [n] */
@@ -302,6 +304,31 @@ typedef struct zkwg_dkim_batch {
 } zkwg_dkim_batch;
 int zkwg_generate_inputs_device(zkwg_circuit_t* c, const zkwg_dkim_batch* batch, uint64_t n_emails,
                                 void* d_records, void* d_gen_status, void* hip_stream);
+
+/* EmailReveal's records from one needle per email: what zkwg_generate_inputs_device writes, and
+ * substringStartIndex / substringLength with it -- nothing of an email is looked at on the host.  Needle i is
+ * bytes[first[i] .. first[i + 1]) (first has n_emails + 1 entries; both are device pointers, the shape of
+ * zkwg_dkim_verify_args.keys / key_first).  The handle says where it is looked for:
+ *   reveal_from_body = 0   first occurrence in the canonical signed header bytes [0, header_len); the body, if the circuit has one,
+ *                          is prepared as zkwg_generate_inputs_device prepares it, shared selector included
+ *   reveal_from_body = 1   first occurrence `pos` in the canonical body bytes [0, body_len), never in the SHA padding; the body's
+ *                          SHA prefix is cut at (pos / 64) * 64: precomputedSHA is the state after those bytes, emailBody the padded
+ *                          body from there on, substringStartIndex = pos - cut.  batch->selector_len must be 0.
+ * A true substring search in both cases.  A needle that spans a "=\r\n" soft line break of the body is not found: the circuit reveals
+ * the canonical bytes, not the decoded ones.  d_gen_status[i]: the codes of zkwg_generate_inputs_device, and
+ *   5 the needle does not occur in the source | 6 the needle occurs more than once in the record's source array (max_header or
+ *   max_body bytes, SHA padding and zero fill included, overlapping occurrences counted: what CountSubstringOccurrences counts) and
+ *   the circuit checks uniqueness | 7 the needle is empty or longer than max_substring.
+ * Order: 1, 3 and 4 as zkwg_generate_inputs_device reports them, then 7, 5, 2 (with the needle's cut), 6.  A record with a code has
+ * a body length of 0 and both index fields 0.
+ * ZKWG_RC_BAD_CONFIG: the handle is not ZKWG_MAIN_EMAIL_REVEAL; ZKWG_RC_BAD_ARG: a null pointer, or a selector with body needles.
+ * One kernel on `hip_stream`: no allocation, no synchronisation. */
+typedef struct zkwg_needles {
+  const uint8_t* bytes;          /* the needles, one behind the other */
+  const uint32_t* first;         /* [n_emails + 1] */
+} zkwg_needles;
+int zkwg_generate_reveal_inputs_device(zkwg_circuit_t* c, const zkwg_dkim_batch* batch, const zkwg_needles* needles,
+                                       uint64_t n_emails, void* d_records, void* d_gen_status, void* hip_stream);
 
 /* Device-resident batch below the boundary: for a host without a tensor library (the Node host of the
  * reference) that feeds a device-side consumer.  The records go to the device once; the compute kernels of sub-batch i + 1

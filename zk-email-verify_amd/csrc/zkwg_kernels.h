@@ -44,3 +44,4 @@ __global__ void zk_o0_rows_small_long(ZkX3 A, ZkO0Dev O);
 __global__ void zk_o0_rows_fr(ZkX3 A, ZkO0Dev O);
 __global__ void zk_mont_convert(Fr* v, u64 n, int to_mont);  // zkwg_kernels_handoff.hip
 __global__ void zk_gen_inputs(ZkSched s, ZkDkimBatch D, u8* recs, int* gen_status, u32 n);  // zkwg_kernels_inputs.hip
+__global__ void zk_gen_reveal_inputs(ZkSched s, ZkDkimBatch D, ZkNeedles Q, u8* recs, int* gen_status, u32 n);

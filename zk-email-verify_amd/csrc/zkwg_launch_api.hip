@@ -403,23 +403,51 @@ int zkwg_calculate_batch_device(zkwg_circuit_t* c, const void* d_in, uint64_t n,
   return zkwg_expand_device(c, d_in, n, d_scratch, 0, n, d_out, out_stride, hip_stream);
 }
 
-int zkwg_generate_inputs_device(zkwg_circuit_t* c, const zkwg_dkim_batch* b, uint64_t n, void* d_records,
-                                void* d_gen_status, void* hip_stream) {
-  if (!c || !b || !d_records || !d_gen_status) return ZKWG_RC_BAD_ARG;
-  if (c->device < 0) return ZKWG_RC_NO_DEVICE;
-  if (c->lay.s.main_kind != ZKWG_MAIN_EMAIL_VERIFIER && !c->lay.s.app.present) return ZKWG_RC_BAD_CONFIG;   // (EmailReveal: its two indices are the caller's)
-  if (n == 0) return ZKWG_RC_OK;
+// what both input generators check of a batch, and its device-side copy
+static int gen_batch(const zkwg_circuit_t* c, const zkwg_dkim_batch* b, ZkDkimBatch& D) {
   if (!b->headers || !b->header_len || !b->pubkey_be || !b->signature_be) return ZKWG_RC_BAD_ARG;
   if (c->lay.s.body && (!b->bodies || !b->body_len || !b->body_hash_b64)) return ZKWG_RC_BAD_ARG;
   if (b->selector_len && !b->selector) return ZKWG_RC_BAD_ARG;
-  ZkDkimBatch D;
   D.headers = b->headers; D.header_len = b->header_len; D.bodies = b->bodies; D.body_len = b->body_len;
   D.body_hash_b64 = b->body_hash_b64; D.pubkey_be = b->pubkey_be; D.signature_be = b->signature_be;
   D.selector = b->selector; D.header_stride = b->header_stride; D.body_stride = b->body_stride;
   D.selector_len = b->selector_len;
+  return ZKWG_RC_OK;
+}
+
+int zkwg_generate_inputs_device(zkwg_circuit_t* c, const zkwg_dkim_batch* b, uint64_t n, void* d_records,
+                                void* d_gen_status, void* hip_stream) {
+  if (!c || !b || !d_records || !d_gen_status) return ZKWG_RC_BAD_ARG;
+  if (c->device < 0) return ZKWG_RC_NO_DEVICE;
+  // (EmailReveal: its two indices are the caller's here; zkwg_generate_reveal_inputs_device finds them)
+  if (c->lay.s.main_kind != ZKWG_MAIN_EMAIL_VERIFIER && !c->lay.s.app.present) return ZKWG_RC_BAD_CONFIG;
+  if (n == 0) return ZKWG_RC_OK;
+  ZkDkimBatch D;
+  const int rc = gen_batch(c, b, D);
+  if (rc != ZKWG_RC_OK) return rc;
   ZkDeviceGuard dg(c->device);
   if (!dg.ok) return ZKWG_RC_HIP_ERROR;
   hipLaunchKernelGGL(zk_gen_inputs, dim3((u32)n), dim3(64), 0, (hipStream_t)hip_stream, c->lay.s, D, (u8*)d_records,
+                     (int*)d_gen_status, (u32)n);
+  return hipGetLastError() == hipSuccess ? ZKWG_RC_OK : ZKWG_RC_HIP_ERROR;
+}
+
+int zkwg_generate_reveal_inputs_device(zkwg_circuit_t* c, const zkwg_dkim_batch* b, const zkwg_needles* nd, uint64_t n,
+                                       void* d_records, void* d_gen_status, void* hip_stream) {
+  if (!c || !b || !nd || !d_records || !d_gen_status) return ZKWG_RC_BAD_ARG;
+  if (c->device < 0) return ZKWG_RC_NO_DEVICE;
+  if (!c->lay.s.app.present) return ZKWG_RC_BAD_CONFIG;
+  if (n == 0) return ZKWG_RC_OK;
+  if (n > 0xffffffffull || !nd->bytes || !nd->first) return ZKWG_RC_BAD_ARG;
+  if (c->lay.s.app.from_body && b->selector_len) return ZKWG_RC_BAD_ARG;      // the needle cuts the body: a selector beside it is refused
+  ZkDkimBatch D;
+  const int rc = gen_batch(c, b, D);
+  if (rc != ZKWG_RC_OK) return rc;
+  ZkNeedles Q;
+  Q.bytes = nd->bytes; Q.first = nd->first;
+  ZkDeviceGuard dg(c->device);
+  if (!dg.ok) return ZKWG_RC_HIP_ERROR;
+  hipLaunchKernelGGL(zk_gen_reveal_inputs, dim3((u32)n), dim3(64), 0, (hipStream_t)hip_stream, c->lay.s, D, Q, (u8*)d_records,
                      (int*)d_gen_status, (u32)n);
   return hipGetLastError() == hipSuccess ? ZKWG_RC_OK : ZKWG_RC_HIP_ERROR;
 }

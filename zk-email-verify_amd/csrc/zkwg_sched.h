@@ -362,6 +362,11 @@ struct ZkDkimBatch {
   const u8* selector;      // shaPrecomputeSelector bytes (shared by the batch) or NULL
   u32 header_stride, body_stride, selector_len;
 };
+// One needle per email (device pointers) -- input of zk_gen_reveal_inputs; = zkwg_needles (include/zkwg.h)
+struct ZkNeedles {
+  const u8* bytes;         // the needles, one behind the other
+  const u32* first;        // [n + 1]: needle e is bytes[first[e], first[e + 1])
+};
 
 #if defined(__HIPCC__)
 // Device pointers of one launch (kernel argument, by value).

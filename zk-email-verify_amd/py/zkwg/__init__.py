@@ -804,16 +804,27 @@ def witness_ints(b):
     return [int.from_bytes(b[i:i + 32], "little") for i in range(0, len(b), 32)]
 
 
-def generate_inputs_device(circuit, dkim_results, selector=None, stream=None, substrings=None):
-    """Batched input generation on the GPU (zkwg_generate_inputs_device).  EmailReveal: substrings = [(start, length), ...],
-    one pair per email, written into the device records' two index fields with a strided copy.  dkim_results: list of dicts with
-    headers, body, bodyHash, publicKey, signature (as `verifyDKIMSignature` returns them), or the handle of
-    zkwg.dkim.verify_batch_device, whose batch is on the device already.  Returns
-    (records: torch.uint8[n, in_stride] on the device, gen_status: list[int])."""
+def generate_inputs_device(circuit, dkim_results, selector=None, stream=None, substrings=None, needles=None):
+    """Batched input generation on the GPU.  dkim_results: list of dicts with headers, body, bodyHash, publicKey, signature (as
+    `verifyDKIMSignature` returns them), or the handle of zkwg.dkim.verify_batch_device, whose batch is on the device already.
+    EmailReveal takes one of
+      needles = [bytes or str, ...]         one per email: the device finds each in the canonical header or body, cuts a body's SHA
+                                            prefix below it and writes the two index fields (zkwg_generate_reveal_inputs_device;
+                                            gen_status 5: absent, 6: not unique, 7: empty or longer than max_substring)
+      substrings = [(start, length), ...]   one pair per email, written into the records of zkwg_generate_inputs_device with a
+                                            strided copy.
+    Returns (records: torch.uint8[n, in_stride] on the device, gen_status: list[int])."""
     import torch
-    from ._lib import DkimBatch
+    from ._lib import DkimBatch, Needles
     dev = torch.device("cuda", circuit.device)
+    reveal = circuit.cfg.main_kind == MAIN_EMAIL_REVEAL
+    if needles is not None and substrings is not None:
+        raise ZkwgError("give needles or substrings, not both")
+    if needles is not None and not reveal:
+        raise ZkwgError("needles go with an EmailReveal circuit, and only with one")
     sel = selector.encode() if isinstance(selector, str) else (selector or b"")
+    if needles is not None and sel and circuit.app.reveal_from_body:
+        raise ZkwgError("a body needle says where the body is cut: a selector beside it is refused")
     t_sel = torch.frombuffer(bytearray(sel or b"\0"), dtype=torch.uint8).to(dev)
     if hasattr(dkim_results, "batch"):
         if dkim_results.batch is None or dkim_results.device != circuit.device:
@@ -844,8 +855,23 @@ def generate_inputs_device(circuit, dkim_results, selector=None, stream=None, su
     recs = torch.empty((n, circuit.in_stride), dtype=torch.uint8, device=dev)
     st = torch.zeros(n, dtype=torch.int32, device=dev)
     sp = stream.cuda_stream if stream is not None else 0
-    if (circuit.cfg.main_kind == MAIN_EMAIL_REVEAL) != (substrings is not None):
-        raise ZkwgError("substrings=[(start, length), ...] goes with an EmailReveal circuit, and only with one")
+    if needles is not None:
+        if len(needles) != n:
+            raise ZkwgError("needles needs one needle per email")
+        nd = [x.encode() if isinstance(x, str) else bytes(x) for x in needles]
+        first = [0]
+        for x in nd:
+            first.append(first[-1] + len(x))
+        if first[-1] >= 1 << 32:
+            raise ZkwgError("the needles are longer than 4 GiB together")
+        t_nb = torch.frombuffer(bytearray(b"".join(nd) or b"\0"), dtype=torch.uint8).to(dev)
+        t_nf = torch.frombuffer(bytearray(b"".join(v.to_bytes(4, "little") for v in first)), dtype=torch.int32).to(dev)
+        q = Needles(t_nb.data_ptr(), t_nf.data_ptr())
+        _check(circuit.lib.zkwg_generate_reveal_inputs_device(circuit.h, C.byref(b), C.byref(q), n, recs.data_ptr(), st.data_ptr(), sp))
+        torch.cuda.synchronize()
+        return recs, st.cpu().tolist()
+    if reveal != (substrings is not None):
+        raise ZkwgError("substrings=[(start, length), ...] or needles=[...] goes with an EmailReveal circuit, and only with one")
     if substrings is not None and len(substrings) != n:
         raise ZkwgError("substrings needs one (start, length) pair per email")
     _check(circuit.lib.zkwg_generate_inputs_device(circuit.h, C.byref(b), n, recs.data_ptr(), st.data_ptr(), sp))

@@ -46,6 +46,10 @@ class DkimBatch(C.Structure):
                 ("selector_len", C.c_uint32)]
 
 
+class Needles(C.Structure):      # zkwg_needles
+    _fields_ = [("bytes", C.c_void_p), ("first", C.c_void_p)]
+
+
 class DkimParsed(C.Structure):   # zkwg_dkim_parsed
     _fields_ = [("status", C.c_int32), ("header_len", C.c_uint32), ("body_offset", C.c_uint64), ("body_len", C.c_uint64),
                 ("header_canon", C.c_uint32), ("body_canon", C.c_uint32), ("has_l", C.c_uint32), ("l", C.c_uint64),
@@ -128,6 +132,7 @@ def load():
         "zkwg_pack_decoded_body": (i32, [vp, vp, vp]),
         "zkwg_calculate_batch": (i32, [vp, vp, u64, vp, u64, vp, u64]),
         "zkwg_generate_inputs_device": (i32, [vp, vp, u64, vp, vp, vp]),
+        "zkwg_generate_reveal_inputs_device": (i32, [vp, vp, vp, u64, vp, vp, vp]),
         "zkwg_alloc_pinned": (vp, [u64]),
         "zkwg_stream_create_masked": (vp, [i32, C.POINTER(C.c_uint32), i32]),
         "zkwg_stream_destroy": (None, [vp]),
@@ -262,7 +267,7 @@ EXPORTS = [
     "zkwg_abi_version", "zkwg_strerror", "zkwg_circuit_create", "zkwg_circuit_create_sym", "zkwg_circuit_create_full", "zkwg_circuit_create_regex", "zkwg_circuit_create_app", "zkwg_regex_info", "zkwg_linear_rows", "zkwg_layout_map", "zkwg_image_layout", "zkwg_segment_table", "zkwg_inverse_table_half", "zkwg_linear_complete_host", "zkwg_o0_gather_host", "zkwg_last_error", "zkwg_circuit_destroy",
     "zkwg_witness_len", "zkwg_witness_bytes", "zkwg_num_public", "zkwg_input_stride",
     "zkwg_input_offset", "zkwg_scratch_bytes", "zkwg_scratch_bytes_standard", "zkwg_pack_input", "zkwg_pack_field", "zkwg_pack_masks", "zkwg_pack_decoded_body", "zkwg_calculate_batch",
-    "zkwg_generate_inputs_device", "zkwg_stream_create_masked", "zkwg_stream_destroy", "zkwg_expand_host", "zkwg_set_host_expand", "zkwg_alloc_pinned", "zkwg_free_pinned", "zkwg_calculate_batch_device", "zkwg_prepare_device", "zkwg_expand_device", "zkwg_expand_montgomery_device", "zkwg_circuit_attach_r1cs", "zkwg_abc_bytes", "zkwg_expand_abc_device", "zkwg_expand_abc_host", "zkwg_expand_full_host", "zkwg_set_prepare_throttle", "zkwg_set_prepare_mask", "zkwg_set_timing", "zkwg_last_kernel_ms", "zkwg_timing_summary", "zkwg_num_kernels",
+    "zkwg_generate_inputs_device", "zkwg_generate_reveal_inputs_device", "zkwg_stream_create_masked", "zkwg_stream_destroy", "zkwg_expand_host", "zkwg_set_host_expand", "zkwg_alloc_pinned", "zkwg_free_pinned", "zkwg_calculate_batch_device", "zkwg_prepare_device", "zkwg_expand_device", "zkwg_expand_montgomery_device", "zkwg_circuit_attach_r1cs", "zkwg_abc_bytes", "zkwg_expand_abc_device", "zkwg_expand_abc_host", "zkwg_expand_full_host", "zkwg_set_prepare_throttle", "zkwg_set_prepare_mask", "zkwg_set_timing", "zkwg_last_kernel_ms", "zkwg_timing_summary", "zkwg_num_kernels",
     "zkwg_kernel_name", "zkwg_kernel_slots", "zkwg_wtns_size", "zkwg_write_wtns", "zkwg_write_sym",
     "zkwg_r1cs_load", "zkwg_r1cs_destroy", "zkwg_r1cs_info", "zkwg_check_constraints_device", "zkwg_r1cs_evaluate_device", "zkwg_check_constraints",
     "zkwg_convert_montgomery_device", "zkwg_shard_range", "zkwg_multi_create", "zkwg_multi_destroy", "zkwg_multi_devices",

@@ -87,9 +87,12 @@ def find_index_in_uint8array(array: bytes, selector: bytes) -> int:
     return -1
 
 
-def generate_partial_sha(body: bytes, body_length: int, selector_string, max_remaining_body_length: int):
-    """sha-utils.ts:30-80."""
-    selector_index = 0
+def generate_partial_sha(body: bytes, body_length: int, selector_string, max_remaining_body_length: int, selector_index=None):
+    """sha-utils.ts:30-80.  selector_index (not the reference's): the position to cut below, in place of the selector's search."""
+    if selector_index is not None:
+        selector_string = None
+    else:
+        selector_index = 0
     if selector_string:
         sel = selector_string.encode() if isinstance(selector_string, str) else selector_string
         selector_index = find_index_in_uint8array(body, sel)
@@ -151,9 +154,10 @@ def generate_email_verifier_inputs_from_dkim_result(dkim, max_headers_length=Non
                                                     ignore_body_hash_check=False, sha_precompute_selector=None,
                                                     enable_header_masking=False, header_mask=None,
                                                     enable_body_masking=False, body_mask=None,
-                                                    remove_soft_line_breaks_flag=False):
+                                                    remove_soft_line_breaks_flag=False, cut_position=None):
     """input-generators.ts:190-252.  `dkim` = dict(headers: bytes, body: bytes, bodyHash: str,
-    publicKey: int, signature: int) -- the DKIMVerificationResult fields the function uses."""
+    publicKey: int, signature: int) -- the DKIMVerificationResult fields the function uses.  cut_position (not the
+    reference's): a position in the body; the SHA prefix is cut at the 64-byte boundary below it, without a selector."""
     headers = dkim["headers"]
     message_padded, message_padded_len = sha256_pad(headers, max_headers_length or MAX_HEADER_PADDED_BYTES)
     inputs = {
@@ -173,12 +177,19 @@ def generate_email_verifier_inputs_from_dkim_result(dkim, max_headers_length=Non
         body_sha_length = ((len(body) + 63 + 65) // 64) * 64
         body_padded, body_padded_len = sha256_pad(body, max(max_body, body_sha_length))
         adjusted_selector = sha_precompute_selector
-        if sha_precompute_selector:
+        if cut_position is not None:
+            if sha_precompute_selector:
+                raise ValueError("a cut position and shaPrecomputeSelector exclude each other")
+            # what remains is the padded body from the cut on, bpad - cut bytes: the zero fill up to bodySHALength, which the
+            # reference slices into bodyRemaining with the rest (64 bytes more than the circuit takes when the cut leaves exactly
+            # maxBodyLength), is not part of it
+            body_padded = body_padded[:body_padded_len]
+        elif sha_precompute_selector:
             clean, pmap = remove_soft_line_breaks(body_padded)
             sel = sha_precompute_selector if isinstance(sha_precompute_selector, str) else sha_precompute_selector.decode()
             adjusted_selector = get_adjusted_selector(body, sel, clean, pmap)
         pre, remaining, remaining_len = generate_partial_sha(body_padded, body_padded_len,
-                                                             adjusted_selector, max_body)
+                                                             adjusted_selector, max_body, cut_position)
         inputs["emailBodyLength"] = str(remaining_len)
         inputs["precomputedSHA"] = [str(b) for b in pre]
         inputs["bodyHashIndex"] = str(body_hash_index)
@@ -227,31 +238,78 @@ def locate_substring(source, needle=None, start=None, length=None, check_uniquen
     return int(start), int(length)
 
 
-def generate_email_reveal_inputs_from_dkim_result(dkim, params=None, needle=None, start=None, length=None):
+def locate_needle(dkim, params, needle):
+    """The rule of zkwg_generate_reveal_inputs_device for one email -> the first position of `needle` in the canonical
+    signed header bytes, or (revealFromBody) in the canonical body bytes: a true substring search that never looks at the SHA padding.
+    ValueError: the needle is empty or longer than maxSubstringLength (where params gives it), or absent."""
+    p = dict(params or {})
+    nd = needle.encode() if isinstance(needle, str) else bytes(needle or b"")
+    if not nd or (p.get("maxSubstringLength") is not None and len(nd) > int(p["maxSubstringLength"])):
+        raise ValueError("the needle is empty or longer than maxSubstringLength")
+    pos = bytes(dkim["body"] if p.get("revealFromBody") else dkim["headers"]).find(nd)
+    if pos < 0:
+        raise ValueError("the needle does not occur in the canonical " + ("body" if p.get("revealFromBody") else "header"))
+    return pos
+
+
+def generate_email_reveal_inputs_from_dkim_result(dkim, params=None, needle=None, start=None, length=None, cut_at_needle=False):
     """generate_email_verifier_inputs_from_dkim_result plus substringStartIndex / substringLength of EmailReveal
     (circuits/email-reveal.circom).  params: maxHeadersLength, maxBodyLength, ignoreBodyHashCheck, shaPrecomputeSelector as for
-    EmailVerifier, and revealFromBody, shouldCheckUniqueness (default 1)."""
+    EmailVerifier, and revealFromBody, shouldCheckUniqueness (default 1), maxSubstringLength (optional: checked when given).
+    cut_at_needle: the needle is the input, as for zkwg_generate_reveal_inputs_device, whose rule this states.  It is
+    looked for in the canonical header or body bytes themselves (locate_needle); with revealFromBody the body's SHA prefix is cut at
+    the 64-byte boundary below it -- shaPrecomputeSelector is refused beside it -- so a body much longer than maxBodyLength
+    needs no selector.  The errors come in the order of the device's codes: header too long (1), selector not found (3), the needle
+    empty or too long (7), absent (5), remaining body too long (2), not unique in the array the circuit sees (6)."""
     p = dict(params or {})
     if p.get("enableHeaderMasking") or p.get("enableBodyMasking") or p.get("removeSoftLineBreaks"):
         raise ValueError("EmailReveal has no masking and no soft-line-break removal")
     if p.get("revealFromBody") and p.get("ignoreBodyHashCheck"):
         raise ValueError("revealFromBody needs the body-hash check")
+    uniq = bool(p.get("shouldCheckUniqueness", 1))
+    if cut_at_needle:
+        if needle is None or start is not None or length is not None:
+            raise ValueError("cut_at_needle takes a needle, not start and length")
+        from_body = bool(p.get("revealFromBody"))
+        if from_body and p.get("shaPrecomputeSelector"):
+            raise ValueError("the needle says where the body is cut: shaPrecomputeSelector is refused beside it")
+        sha256_pad(dkim["headers"], p.get("maxHeadersLength") or MAX_HEADER_PADDED_BYTES)                       # (1)
+        if p.get("shaPrecomputeSelector") and not p.get("ignoreBodyHashCheck"):                                  # (3)
+            max_body = p.get("maxBodyLength") or MAX_BODY_PADDED_BYTES
+            padded, padded_len = sha256_pad(dkim["body"], max(max_body, ((len(dkim["body"]) + 63 + 65) // 64) * 64))
+            sel = p["shaPrecomputeSelector"]
+            sel = sel if isinstance(sel, str) else sel.decode()
+            adjusted = get_adjusted_selector(dkim["body"], sel, *remove_soft_line_breaks(padded))
+            if find_index_in_uint8array(padded, adjusted.encode()) < 0:
+                raise ValueError(f'SHA precompute selector "{adjusted}" not found in the body')
+        pos = locate_needle(dkim, p, needle)                                                                    # (7), (5)
+        inputs = generate_email_verifier_inputs_from_dkim_result(
+            dkim, p.get("maxHeadersLength"), p.get("maxBodyLength"), bool(p.get("ignoreBodyHashCheck")), p.get("shaPrecomputeSelector"),
+            cut_position=pos if from_body else None)                                                            # (2)
+        nd = needle.encode() if isinstance(needle, str) else bytes(needle)
+        src = bytes(int(b) for b in inputs["emailBody" if from_body else "emailHeader"])
+        at = pos - (pos // 64) * 64 if from_body else pos
+        assert src[at:at + len(nd)] == nd and src.find(nd) == at
+        if uniq and src.find(nd, at + 1) >= 0:                                                                  # (6)
+            raise ValueError("the needle occurs more than once and the circuit checks uniqueness")
+        inputs["substringStartIndex"], inputs["substringLength"] = str(at), str(len(nd))
+        return inputs
     inputs = generate_email_verifier_inputs_from_dkim_result(dkim, p.get("maxHeadersLength"), p.get("maxBodyLength"),
                                                              bool(p.get("ignoreBodyHashCheck")), p.get("shaPrecomputeSelector"))
-    a, n = locate_substring(inputs["emailBody" if p.get("revealFromBody") else "emailHeader"], needle, start, length,
-                            bool(p.get("shouldCheckUniqueness", 1)))
+    a, n = locate_substring(inputs["emailBody" if p.get("revealFromBody") else "emailHeader"], needle, start, length, uniq)
     inputs["substringStartIndex"], inputs["substringLength"] = str(a), str(n)
     return inputs
 
 
 def generate_email_reveal_inputs(raw_eml, params=None, keys=None, needle=None, start=None, length=None, dkim_verification_args=None,
-                                 device=0):
+                                 device=0, cut_at_needle=False):
     """A raw email -> the CircuitInput of EmailReveal: verifyDKIMSignature, EmailVerifier's inputs, and the position of
-    `needle` (or start / length) in the canonical header or body the circuit sees."""
+    `needle` (or start / length) in the canonical header or body the circuit sees.  cut_at_needle: see
+    generate_email_reveal_inputs_from_dkim_result."""
     from . import dkim
     a = dict(dkim_verification_args or {})
     result = dkim.verify_dkim_signature(raw_eml, a.get("domain") or "", a.get("enableSanitization", True), keys=keys, device=device)
-    return generate_email_reveal_inputs_from_dkim_result(result, params, needle, start, length)
+    return generate_email_reveal_inputs_from_dkim_result(result, params, needle, start, length, cut_at_needle)
 
 
 def clean_email_address(addr):
